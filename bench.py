@@ -20,13 +20,19 @@ max over ranks and value = all ranks' checksummed bytes / that time.
 `--dry-run` runs the same sharding on the CPU (gloo, no GPU call) and checks
 that the ranks cover every block exactly once.
 
-Also reported: per-kernel roofline (HIP events on the launch stream, and the
-kernel-trace average of the committed rocprofv3 profile of the same config),
-HBM traffic from the committed PMC summary, the CPU baseline (oracle = our
-restatement, timed on this host), the north-star point (1 M x 16 KiB, CRC32C
-and XXH3), C3/C4, the legacy kxxHash / kxxHash64 types, the WAL config C5,
-per-KV protection (a15) and the PCIe-inclusive end-to-end rates (DESIGN.md
-§6).  At N = 1 with extras, bench.py runs the headline config and each extra
+A plain run (`--gpus 1 --steps K --warmup W`) sets up the batch, warms up,
+times the K steps and prints the result line: the headline value, ms_per_step
+and the per-kernel roofline of those same steps (HIP events on the launch
+stream, beside the kernel-trace average and HBM traffic read from the
+committed rocprofv3 summary of the config).  `--dump-outputs DIR` also writes
+what the last timed step computed as DIR/<name>.npy (dump_outputs below); the
+inputs are seeded, so two builds can be compared output for output.
+
+`--full` adds everything that takes runs of its own: the CPU baseline (oracle
+= our restatement, timed on this host), the north-star point (1 M x 16 KiB,
+CRC32C and XXH3), C3/C4, the legacy kxxHash / kxxHash64 types, the WAL config
+C5, per-KV protection (a15) and the PCIe-inclusive end-to-end rates (DESIGN.md
+§6).  At N = 1 with `--full`, bench.py runs the headline config and each extra
 in a child process of its own (this process never touches the GPU) and prints
 the merged line: each measurement starts from a fresh device allocation
 state.
@@ -157,11 +163,49 @@ def run_config(name, steps, warmup, rank, world):
                        "gibs_checksummed": b.checksummed_bytes / t_vf / GIB},
         },
         "batch": b,
+        "outputs": {"computed": comp, "ok": ok, "mismatches": bad},
     }
     for k in res["kernels"].values():
         k["achieved_gbs"] = k["alg_bytes"] / k["avg_s"] / 1e9
         k["frac"] = k["achieved_gbs"] / HBM_PEAK_GBS
     return res
+
+
+DUMP_BUDGET = 64 << 20  # bytes of .npy payload, all ranks together
+DUMP_ROW = 5 * 4 + 8 + 4 + 8  # trailers f32 x5, computed f64, ok f32, block_index f64
+
+
+def dump_outputs(out_dir, res, b, rank, world):
+    """--dump-outputs: what the last timed step left for its caller, as .npy:
+    trailers    [k, 5] float32  the [type][LE32] bytes the trailer pass wrote
+                                after each block (block_trailer_batch, in place)
+    computed    [k]    float64  the checksum the verify pass computed per block
+    ok          [k]    float32  its per-block verdict
+    mismatches  [1]    float64  its mismatch counter (summed over the timed steps)
+    block_index [k]    float64  which blocks of this rank's shard the rows are:
+                                all of them while they fit the 64 MB budget,
+                                else a fixed sample (seeded, sorted)
+    At N > 1 each rank writes <name>.rank<r>.npy and takes 1/N of the budget."""
+    n = b.n
+    k = min(n, DUMP_BUDGET // world // DUMP_ROW)
+    if k < n:
+        sel = np.sort(np.random.default_rng(0xD0FF + rank).choice(n, k, replace=False))
+    else:
+        sel = np.arange(n)
+    dsel = torch.from_numpy(sel).cuda()
+    end = b.offsets[dsel].to(torch.int64) + b.sizes[dsel].to(torch.int64)
+    trailers = b.base[end[:, None] + torch.arange(5, device="cuda")[None, :]]
+    o = res["outputs"]
+    arrays = {"trailers": trailers.cpu().numpy().astype(np.float32),
+              "computed": o["computed"].view(torch.int32)[dsel].cpu().numpy()
+                                       .view(np.uint32).astype(np.float64),
+              "ok": o["ok"][dsel].cpu().numpy().astype(np.float32),
+              "mismatches": o["mismatches"].cpu().numpy().astype(np.float64),
+              "block_index": sel.astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f".rank{rank}" if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
 
 
 def run_wal(steps, warmup, n_records=10_000_000):
@@ -719,15 +763,16 @@ EXTRA_SST = ("NS16", "NS16X", "C3", "C3S", "C4", "NS16H32", "NS16H64")
 
 
 def orchestrate(args):
-    """N = 1 with extras: the headline config (plus the CPU baseline and the
+    """N = 1 with --full: the headline config (plus the CPU baseline and the
     host-memory paths) and every extra run in a child process of its own, one
     after the other, so each starts from a fresh device allocation state (in
     one process, a 28 GiB batch allocated after another one measured 3-7 %
     slower: C3 / C3S in BENCH_r04, bench_r05a).  This process never touches
     the GPU; it merges the children's lines into the one JSON line."""
     common = ["--steps", str(args.steps), "--warmup", str(args.warmup)]
-    line = run_child(["--config", args.config, "--child"] + common +
-                     (["--no-cpu-baseline"] if args.no_cpu_baseline else []))
+    line = run_child(["--config", args.config, "--full", "--child"] + common +
+                     (["--no-cpu-baseline"] if args.no_cpu_baseline else []) +
+                     (["--dump-outputs", args.dump_outputs] if args.dump_outputs else []))
     extras = line.setdefault("extras", {})
     for nm in EXTRA_SST + ("C5_wal", "a15_kv"):
         try:
@@ -770,9 +815,15 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="C2", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baseline and the extras (north-star, C3/C4, legacy "
+                         "types, C5 WAL, per-KV protection, PCIe-inclusive and host-memory paths)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="(with --full) skip the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip north-star, C3/C4, C5 and end-to-end extras")
+                    help="(with --full) skip north-star, C3/C4, C5 and end-to-end extras")
     ap.add_argument("--dry-run", action="store_true",
                     help="shard the described batch on the CPU (gloo) without a GPU")
     ap.add_argument("--child", action="store_true",
@@ -784,7 +835,7 @@ def main():
     if args.extra:
         print(json.dumps(run_extra(args.extra, args.steps, args.warmup)), flush=True)
         return
-    if (args.gpus == 1 and "WORLD_SIZE" not in os.environ and not args.dry_run and
+    if (args.full and args.gpus == 1 and "WORLD_SIZE" not in os.environ and not args.dry_run and
             not args.child and not args.no_extras and args.config == "C2"):
         sys.exit(orchestrate(args))
 
@@ -802,11 +853,14 @@ def main():
     engine.init_device()
     main_res = run_config(args.config, args.steps, args.warmup, rank, world)
     b = main_res.pop("batch")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, main_res, b, rank, world)
+    main_res.pop("outputs")
     extras = {}
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(b, main_res["ctype"])
-    if world == 1 and (args.child or not args.no_extras):
+    if args.full and world == 1 and (args.child or not args.no_extras):
         try:
             # the first pass pays one-time costs (host pinning, first touch of
             # the staging buffers): best of 3 passes, the first reported too
@@ -821,7 +875,7 @@ def main():
             extras["host_memory_verify_error"] = str(e)
     del b
     torch.cuda.empty_cache()
-    if world > 1 and not args.no_extras:
+    if args.full and world > 1 and not args.no_extras:
         # (no try: every rank takes part in its barriers; a failure ends the run)
         extras["C5_wal_verify_sharded"] = run_wal_sharded(max(3, args.steps // 2), 1, rank, world)
         torch.cuda.empty_cache()

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """tests/golden/refbuild.py -- TEST INFRASTRUCTURE ONLY: compile the
 REFERENCE's own library sources (the LIB_SOURCES list of /root/reference/src.mk)
-with g++ into a throwaway directory OUTSIDE the repository, archive them, and
+with g++ into a cache directory that is never committed, archive them, and
 link a fixture veneer against that archive.
 
 Why an archive: the reference objects we need (log::Reader, SstFileWriter /
@@ -22,7 +22,8 @@ Compression: only zlib has headers in the image, so -DZLIB (kZlibCompression);
 snappy / lz4 / zstd / bzip2 are compiled out exactly as a reference build
 without those libraries would be.
 
-Objects are cached under $FORST_REFOBJ (default /tmp/forst_refobj), keyed by
+Objects are cached under $FORST_REFOBJ (default oracle/_ref/refobj in this
+tree, which git ignores), keyed by
 flags, so the generators can be re-run cheaply.  Nothing produced here is
 committed; the generators commit only data (inputs and expected outputs).
 """
@@ -34,7 +35,9 @@ import sys
 from concurrent.futures import ThreadPoolExecutor
 
 REF = os.environ.get("FORST_REFERENCE", "/root/reference")
-CACHE = os.environ.get("FORST_REFOBJ", "/tmp/forst_refobj")
+CACHE = os.environ.get("FORST_REFOBJ") or os.path.join(
+    os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))),
+    "oracle", "_ref", "refobj")
 DEFS = ["-DROCKSDB_PLATFORM_POSIX", "-DROCKSDB_LIB_IO_POSIX", "-DOS_LINUX", "-DZLIB",
         "-DNDEBUG", "-DROCKSDB_SUPPORT_THREAD_LOCAL"]
 CXXFLAGS = ["-std=c++17", "-O1", "-fPIC", "-ffunction-sections", "-fdata-sections", "-w",

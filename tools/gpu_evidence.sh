@@ -1,7 +1,7 @@
 #!/bin/bash
 # evidence at the current build: the whole -m gpu suite and smoke,
 # rocprofv3 kernel trace + FETCH/WRITE passes for the configs (C5 split by
-# call site), then the default bench line.  TAG names the profiles.
+# call site), then the full bench line.  TAG names the profiles.
 set -eo pipefail
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export TMPDIR=/tmp
@@ -20,6 +20,6 @@ if [ -z "$NOPROF" ]; then
   done
 fi
 if [ -z "$NOBENCH" ]; then
-  timeout -k 10 900 python -u bench.py > "$OUT/bench.log" 2>&1 || { tail -20 "$OUT/bench.log"; exit 1; }
+  timeout -k 10 900 python -u bench.py --full > "$OUT/bench.log" 2>&1 || { tail -20 "$OUT/bench.log"; exit 1; }
   tail -1 "$OUT/bench.log"
 fi
