@@ -1782,7 +1782,9 @@ __device__ __forceinline__ void crc32c_rows_body(const BlockArgs& a) {
           // byte store per wave instead of five per finishing row
           const uint32_t k = t - 11;
           if (!staged && calc && valid && (k != 0 || a.last_bytes)) {
-            uint8_t* pw = a.base_w + C.template end<MODE>(mem_last_byte<MODE>(a));
+            // (slow rows keep the block offset in tp and their size in pk)
+            uint8_t* pw = a.base_w + (C.slow() ? C.tp() + C.slow_size()
+                                               : C.template end<MODE>(mem_last_byte<MODE>(a)));
             pw[k] = static_cast<uint8_t>(k == 0 ? cu.extra : out >> (8 * (k - 1)));
           }
         }

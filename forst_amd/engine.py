@@ -168,23 +168,24 @@ def xxh3_64_batch(base, offsets, lengths, out=None, stream=None):
 
 
 def wal_verify_batch(log, log_number=0, first_block=0, n_blocks=None, bad_blocks=None,
-                     stream=None):
+                     stream=None, status=True, nrec=True, fail_off=True):
     """Physical-record CRC verification of 32 KiB log blocks
-    (db/log_reader.cc:450-531).  Returns (status, nrec, fail_off, bad_blocks)."""
+    (db/log_reader.cc:450-531).  Returns (status, nrec, fail_off, bad_blocks)
+    (None where not asked; a tensor given for an output is filled)."""
     _dev_u8(log)
     total = (log.numel() + 32767) // 32768
     if n_blocks is None:
         n_blocks = total - first_block
     dev = log.device
-    status = torch.empty(n_blocks, dtype=torch.uint8, device=dev)
-    nrec = torch.empty(n_blocks, dtype=torch.uint32, device=dev)
-    fail = torch.empty(n_blocks, dtype=torch.uint32, device=dev)
+    st = torch.empty(n_blocks, dtype=torch.uint8, device=dev) if status is True else status
+    nr = torch.empty(n_blocks, dtype=torch.uint32, device=dev) if nrec is True else nrec
+    fo = torch.empty(n_blocks, dtype=torch.uint32, device=dev) if fail_off is True else fail_off
     if bad_blocks is None:
         bad_blocks = torch.zeros(1, dtype=torch.int64, device=dev)
     check(lib().forst_wal_verify_batch(log.data_ptr(), log.numel(), first_block, n_blocks,
-                                       log_number, status.data_ptr(), nrec.data_ptr(),
-                                       fail.data_ptr(), bad_blocks.data_ptr(), _stream(stream)))
-    return status, nrec, fail, bad_blocks
+                                       log_number, _p(st), _p(nr), _p(fo),
+                                       bad_blocks.data_ptr(), _stream(stream)))
+    return st, nr, fo, bad_blocks
 
 
 def wal_record_crc_batch(log, header_offsets, write_in_place=True, out=None, stream=None,

@@ -618,3 +618,32 @@ def test_emu_wal_record_xxh3_unpacked_form(recyclable):
         h, f = emu.wal_record_xxh3(buf, po)
     assert len(h) == len(lens)
     assert (np.asarray(h).view(np.uint64) == W.expected_hashes(payload, lens)).all()
+
+
+def test_emu_crc_trailer_direct_stores_of_tiny_blocks():
+    """trailer mode with a workgroup range longer than the result stage
+    (kStageW = 6144 results; the emulator's grid is 2 workgroups): the
+    trailers past it are stored by the rows themselves, and a block without
+    one whole dword (the slow rows) keeps its offset and size in another form
+    than the fast rows -- its trailer went 4..8 bytes too far.  The whole
+    image against the oracle's: every trailer byte, no other byte."""
+    rng = np.random.default_rng(19)
+    sizes = np.concatenate([np.repeat(np.arange(24), 16), rng.integers(0, 40, 15000)])
+    sizes = sizes[rng.permutation(len(sizes))].astype(np.uint32)
+    offs = np.zeros(len(sizes), np.uint64)
+    offs[1:] = np.cumsum(sizes[:-1].astype(np.uint64) + 5 + rng.integers(0, 3, len(sizes) - 1)
+                         .astype(np.uint64))
+    total = int(offs[-1]) + int(sizes[-1]) + 5
+    base = rng.integers(0, 256, total, dtype=np.uint8)
+    types = rng.integers(0, 256, len(sizes), dtype=np.uint8)
+    mods = rng.integers(0, 2**32, len(sizes), dtype=np.uint64).astype(np.uint32)
+    img, out = emu.block_trailer(1, base, offs, sizes, types, mods)
+    want = O.block_checksum_batch(1, base, offs, sizes, last_bytes=types, modifiers=mods)
+    assert (out == want).all()
+    exp = base.copy()
+    end = (offs + sizes).astype(np.int64)
+    exp[end] = types
+    for k in range(4):
+        exp[end + 1 + k] = (want >> np.uint32(8 * k)).astype(np.uint8)
+    bad = np.nonzero(img != exp)[0]
+    assert bad.size == 0, (bad.size, bad[:8].tolist())

@@ -77,9 +77,11 @@ def test_crc32c_extend_with_init(golden):
 @pytest.mark.parametrize("mean", [600, 5000, 40000])
 def test_crc32c_extend_multi_round_with_init(mean):
     """crc32c::Extend(init, data, n) with a per-message init over messages of
-    1..~3 x mean bytes at every alignment, from the buffer start on: the rows
-    kernel (mean <= 20 KiB) and the v2 kernel take the init in round 0 of a
-    message, many rounds before its finish"""
+    1..~3 x mean bytes at every alignment, from the buffer start on: the init
+    is taken in round 0 of a message, many rounds before its finish.  With
+    3000 messages this is crc32c_rows_raw_small_kernel at every mean (a raw
+    batch under 64 * 16 descriptors per workgroup of the grid); the lane and
+    filter kernels of larger batches are covered by tests/test_gpu_paths.py"""
     rng = np.random.default_rng(mean)
     n = 3000
     sizes = rng.integers(1, 3 * mean, n).astype(np.uint32)
