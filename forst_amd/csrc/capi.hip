@@ -26,7 +26,6 @@ namespace {
 
 thread_local std::string g_last_error;
 thread_local const char* g_last_kernel = "";
-thread_local std::string g_last_kernel_buf;
 
 constexpr int kMaxDevices = 64;
 DeviceInfo g_info[kMaxDevices];
@@ -183,34 +182,11 @@ void aux_pool_stats(uint32_t* live, uint32_t* idle) {
   if (idle) *idle = n;
 }
 
-#ifdef FORST_DIAG
-const char* diag_env(const char* name) {
-  const char* v = std::getenv(name);
-  return v ? v : "";
-}
-#endif
-
 hipError_t feed_setup(BlockArgs& a, uint64_t nw, hipStream_t stream) {
   // half the descriptors as equal static shares (no claims while the
   // machine fills), the rest in claimed 64-descriptor chunks that absorb
   // the byte imbalance of mixed block sizes
   a.ticket = nullptr;
-#ifdef FORST_DIAG
-  const std::string mode = diag_env("FORST_FEED");
-  if (mode == "static") {  // one contiguous share per wave (A/B reference)
-    a.share1 = (a.n + 64 * nw - 1) / (64 * nw) * 64;
-    if (a.share1 * nw > a.n) a.share1 = a.n / (64 * nw) * 64;
-    return hipSuccess;
-  }
-  if (mode == "rr") {  // round-robin chunks, no counter (A/B reference)
-    a.share1 = a.n / (2 * 64 * nw) * 64;
-    return hipSuccess;
-  }
-  if (mode == "rr0") {  // round-robin chunks only: every wave sweeps the buffer in step
-    a.share1 = 0;
-    return hipSuccess;
-  }
-#endif
   a.share1 = a.n / (2 * 64 * nw) * 64;
   void* p = nullptr;
   hipError_t e = scratch_alloc(&p, 64 * sizeof(unsigned long long), stream);
@@ -246,72 +222,6 @@ int check_block_args(const uint8_t* base, const uint64_t* offsets, const uint32_
   return FORST_OK;
 }
 
-// trailer bytes [type][LE32 out] at each block end (split write side: the
-// streaming kernel runs in compute mode, the in-place writes come after it)
-__global__ void __launch_bounds__(256) trailer_scatter_kernel(BlockArgs a) {
-  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
-  if (i >= a.n) return;
-  const uint64_t off = a.offsets[i];
-  const uint32_t n = a.sizes[i];
-  if (off > a.base_len || uint64_t(n) + 5 > a.base_len - off) return;
-  uint8_t* p = a.base_w + off + n;
-  const uint32_t v = a.out32[i];
-  p[0] = a.last_bytes[i];
-  p[1] = static_cast<uint8_t>(v);
-  p[2] = static_cast<uint8_t>(v >> 8);
-  p[3] = static_cast<uint8_t>(v >> 16);
-  p[4] = static_cast<uint8_t>(v >> 24);
-}
-
-hipError_t launch_blocks(int type, int mode, const BlockArgs& a, hipStream_t s);
-
-int dispatch_blocks(int type, int mode, const BlockArgs& a, void* stream) {
-  int rc = check_device();
-  if (rc) return rc;
-  if (type < FORST_kNoChecksum || type > FORST_kXXH3)  // options_helper.h:34
-    return set_error(FORST_EINVAL, "unknown ChecksumType " + std::to_string(type));
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  // Write side: the 5 trailer bytes per block are partial writes into 64 B
-  // memory sectors shared with block data (a read-modify-write below the
-  // L2).  Stored by the streaming kernel as rows finish they cost 16 % of
-  // the pass (C2, round 1), split off into a second, tiny kernel 8 %.  Since
-  // round 4 the rows kernels stage a workgroup's results in LDS and write
-  // them after their loop, which beats the split form (C2 write side -1.4 %,
-  // NS16X -0.2 %, profiles/ab_r04/trailer_fused_staged.log);
-  // FORST_TRAILER_SPLIT=1 builds the split form.
-  // (diagnostics build: FORST_TRAILER=fused|split at run time)
-#ifndef FORST_TRAILER_SPLIT
-#define FORST_TRAILER_SPLIT 0
-#endif
-  bool split = FORST_TRAILER_SPLIT;
-#ifdef FORST_DIAG
-  if (*diag_env("FORST_TRAILER")) split = std::string(diag_env("FORST_TRAILER")) != "fused";
-#endif
-  if (mode == kModeTrailer && split && a.n) {
-    BlockArgs c = a;
-    void* tmp = nullptr;
-    hipError_t e = hipSuccess;
-    if (!c.out32) {
-      e = scratch_alloc(&tmp, 4 * a.n, s);
-      c.out32 = static_cast<uint32_t*>(tmp);
-    }
-    if (e == hipSuccess) e = launch_blocks(type, kModeCompute, c, s);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(trailer_scatter_kernel, dim3(static_cast<uint32_t>((a.n + 255) / 256)),
-                         dim3(256), 0, s, c);
-      e = hipGetLastError();
-      g_last_kernel_buf = std::string(g_last_kernel) + "+trailer_scatter_kernel";
-      g_last_kernel = g_last_kernel_buf.c_str();
-    }
-    if (tmp) {
-      const hipError_t f = scratch_free(tmp, s);
-      if (e == hipSuccess) e = f;
-    }
-    return hip_status(e, "kernel launch");
-  }
-  return hip_status(launch_blocks(type, mode, a, s), "kernel launch");
-}
-
 hipError_t launch_blocks(int type, int mode, const BlockArgs& a, hipStream_t s) {
   hipError_t e;
   switch (type) {
@@ -332,6 +242,23 @@ hipError_t launch_blocks(int type, int mode, const BlockArgs& a, hipStream_t s) 
       return hipErrorInvalidValue;
   }
   return e;
+}
+
+int dispatch_blocks(int type, int mode, const BlockArgs& a, void* stream) {
+  int rc = check_device();
+  if (rc) return rc;
+  if (type < FORST_kNoChecksum || type > FORST_kXXH3)  // options_helper.h:34
+    return set_error(FORST_EINVAL, "unknown ChecksumType " + std::to_string(type));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // Write side: the 5 trailer bytes per block are partial writes into 64 B
+  // memory sectors shared with block data (a read-modify-write below the
+  // L2).  Stored by the streaming kernel as rows finish they cost 16 % of
+  // the pass (C2, round 1), split off into a second, tiny kernel 8 %.  Since
+  // round 4 the rows kernels stage a workgroup's results in LDS and write
+  // them after their loop, which beats the split form (C2 write side -1.4 %,
+  // NS16X -0.2 %, profiles/ab_r04/trailer_fused_staged.log), so trailer mode
+  // is one launch like the others.
+  return hip_status(launch_blocks(type, mode, a, s), "kernel launch");
 }
 
 }  // namespace

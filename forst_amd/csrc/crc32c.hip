@@ -21,9 +21,6 @@
 //    compression-type byte on the write side) are appended byte-wise.
 // The combine constants are block-size independent, so mixed 4/16/64 KiB
 // batches run in one launch.  See DESIGN.md for the roofline analysis.
-#include <cstdlib>
-#include <string>
-
 #include "crc32c_tables.h"
 #include "device_common.h"
 #include "engine.h"
@@ -206,318 +203,6 @@ __device__ __forceinline__ void fill_tables(uint32_t* L) {
     L[kOffTree + i] = kCrcTree[i];
   __syncthreads();
 }
-
-#ifdef FORST_DIAG
-// ---------------------------------------------------------------------------
-// Streaming block kernel v1 (diagnostics build only: A/B reference of v2).
-//
-// Each wave owns a contiguous share [kbeg, kend) of the descriptors and walks
-// it as a stream of (block, round) steps.  At the top of every step it issues
-// the global loads of the NEXT step (next round of this block, or round 0 of
-// the next block, plus that block's tail/trailer dwords), then runs the
-// LDS-table CRC of the current step on the registers loaded one step earlier.
-// Every load is unconditional and issued in straight-line code, so the
-// compiler's s_waitcnt for the current step counts only the next step's loads
-// (vmcnt(6)) and one round stays in flight per wave while it computes.  Block
-// descriptors are fetched 64 at a time (lane j holds block kb+j; read with
-// v_readlane into SGPRs) and results are kept in lane kk of result VGPRs and
-// stored once per 64 blocks: no descriptor load or store sits between a
-// prefetch and its use.
-//
-// Head of a message (round 0): the window [W0, Wend) ends at the last dword
-// boundary Wend <= end.  Lanes wholly in front of the first message dword
-// load the last window segment instead (any in-window address is safe) and
-// zero their state; the lane LA holding the first message dword restarts its
-// chain at dword jA with state S0 = ~init moved back over the m = A&3 bytes
-// in front of the message (inverse Sarwate steps), those bytes masked to zero.
-// Tail: the <= 3 bytes after Wend come from the tail dword, byte-wise.
-// Blocks shorter than 64 bytes, blocks whose round-0 head lane would read in
-// front of the buffer, and out-of-range descriptors take the wave_crc32c path.
-// ---------------------------------------------------------------------------
-constexpr uint32_t kOffTinv = kLdsDwords;  // 256-byte inverse of T3's top byte
-constexpr uint32_t kLdsDwordsStream = kLdsDwords + 64;
-static_assert(kLdsDwordsStream * 4 <= 160 * 1024, "stream kernel LDS");
-
-__device__ __forceinline__ void fill_tinv(uint32_t* L) {
-  // Sarwate table T = G[3]: the top byte of T[b] is a bijection of b
-  uint8_t* inv = reinterpret_cast<uint8_t*>(L + kOffTinv);
-  const uint32_t t = threadIdx.x;
-  if (t < 256) inv[kCrcG[3 * 256 + t] >> 24] = static_cast<uint8_t>(t);
-  __syncthreads();
-}
-
-// inverse of one zero-byte step s' = (s >> 8) ^ T[s & 255] (uniform value)
-__device__ __forceinline__ uint32_t crc_unstep(const uint32_t* __restrict__ L, uint32_t lb,
-                                               uint32_t sp) {
-  const uint32_t top = sp >> 24;
-  const uint32_t b = (L[kOffTinv + (top >> 2)] >> (8 * (top & 3))) & 0xffu;
-  const uint32_t t = L[(((b << 7) + lb) >> 2) + 24576];
-  return ((sp ^ t) << 8) | b;
-}
-
-// wave-uniform description of one block (lives in SGPRs)
-struct Blk {
-  uint64_t off;     // message start (offset from base)
-  int64_t w0;       // round-0 window start offset (may be < 0 for slow blocks)
-  uint64_t we;      // window end (dword boundary <= message end)
-  uint64_t t0, t1;  // tail / trailer dword offsets (always loadable)
-  uint32_t size, len, mod, extra;
-  uint32_t R, LA, jA, nt, S0, bm;
-  bool valid, slow;
-};
-
-template <int MODE>
-__device__ __forceinline__ Blk blk_setup(const BlockArgs& a, const uint32_t* __restrict__ L,
-                                         uint32_t lb, uint64_t k, uint64_t kend, uint64_t kb,
-                                         const DescBatch& cb, const DescBatch& nb,
-                                         const uint32_t (&kS0)[4]) {
-  Blk b;
-  const Desc d = batch_desc(k, kb, cb, nb);  // k may be >= kend (then invalid)
-  b.off = d.off;
-  b.size = d.size;
-  b.mod = d.mod;
-  b.extra = d.extra;
-
-  const bool has_extra = (MODE == kModeCompute || MODE == kModeTrailer) && a.last_bytes;
-  const bool mem_last = MODE == kModeVerify || ((MODE == kModeCompute || MODE == kModeTrailer) &&
-                                                !a.last_bytes);
-  b.valid = k < kend && desc_in_range<MODE>(a, d);
-  (void)has_extra;
-  b.len = b.size + (mem_last ? 1u : 0u);
-
-  const uint64_t E = b.off + b.len;
-  const uint64_t ws = b.off & ~3ull;
-  b.we = E & ~3ull;
-  const uint64_t d4 = b.we - ws;
-  b.R = static_cast<uint32_t>((d4 + kRB - 1) / kRB);
-  b.w0 = static_cast<int64_t>(b.we) - static_cast<int64_t>(b.R) * kRB;
-  const uint32_t hA = static_cast<uint32_t>(static_cast<int64_t>(ws) - b.w0);
-  b.LA = hA >> 6;
-  b.jA = (hA >> 2) & 15u;
-  b.nt = static_cast<uint32_t>(E - b.we);
-  const uint32_t m = static_cast<uint32_t>(b.off & 3);
-  b.bm = 0xffffffffu << (8 * m);
-  b.slow = !b.valid || d4 < 64 || b.w0 + 64 * static_cast<int64_t>(b.LA) < 0;
-  if (MODE == kModeRaw) {
-    uint32_t s0 = ~b.extra;
-    for (uint32_t q = 0; q < m; ++q) s0 = crc_unstep(L, lb, s0);
-    b.S0 = s0;
-  } else {
-    b.S0 = m == 0 ? kS0[0] : m == 1 ? kS0[1] : m == 2 ? kS0[2] : kS0[3];
-  }
-  b.t0 = (b.nt > 0 || MODE == kModeVerify) ? b.we : b.we - 4;
-  b.t1 = (MODE == kModeVerify && b.nt > 0) ? b.we + 4 : b.t0;
-  if (b.slow) {  // loads of a slow block's step are dummies at the buffer start
-    b.w0 = 0;
-    b.we = 64;
-    b.LA = 0;
-    b.t0 = b.t1 = 0;
-  }
-  return b;
-}
-
-struct StepBuf {
-  uint32_t w[16];
-  uint32_t t0, t1;
-};
-
-__device__ __forceinline__ void issue_step(const uint8_t* __restrict__ base, uint32_t lane,
-                                           int64_t w0, uint64_t we, uint32_t la, uint64_t t0,
-                                           uint64_t t1, uint32_t r, StepBuf& b) {
-  int64_t so = w0 + static_cast<int64_t>(r) * kRB + 64 * static_cast<int64_t>(lane);
-  const uint32_t la0 = r == 0 ? la : 0u;
-  so = lane < la0 ? static_cast<int64_t>(we) - 64 : so;
-  const uint8_t* sp = base + so;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const u32x4a4 v = ld16_a4(sp + 16 * q);
-    b.w[4 * q + 0] = v.x;
-    b.w[4 * q + 1] = v.y;
-    b.w[4 * q + 2] = v.z;
-    b.w[4 * q + 3] = v.w;
-  }
-  b.t0 = ld4v(base + t0);
-  b.t1 = ld4v(base + t1);
-}
-
-__device__ __forceinline__ uint32_t stream_round(const uint32_t* __restrict__ L, uint32_t lb,
-                                                 uint32_t lane, const Blk& c, uint32_t r,
-                                                 uint32_t s, const uint32_t (&w)[16]) {
-  if (r == 0) {
-    s = 0;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      uint32_t x = s ^ w[q];
-      if (static_cast<uint32_t>(q) == c.jA) {
-        const uint32_t head = (w[q] & c.bm) ^ c.S0;
-        x = lane == c.LA ? head : x;
-      }
-      s = crc_g(L, lb, x);
-    }
-    s = lane < c.LA ? 0u : s;
-  } else {
-    s = crc_shift(L, kOffJump, s);
-#pragma unroll
-    for (int q = 0; q < 16; ++q) s = crc_g(L, lb, s ^ w[q]);
-  }
-  return s;
-}
-
-template <int K>
-__device__ __forceinline__ uint32_t tree_level(const uint32_t* __restrict__ L, uint32_t lane,
-                                               uint32_t s) {
-  const uint32_t other = static_cast<uint32_t>(
-      __builtin_amdgcn_update_dpp(0, static_cast<int>(s), 0x110 + (1 << K), 0xf, 0xf, false));
-  constexpr uint32_t keep = (2u << K) - 1u;
-  if ((lane & keep) == keep) s = crc_shift(L, kOffTree + 1024u * K, other) ^ s;
-  return s;
-}
-
-// combine the 64 lane states of a block (lane l = bytes [64l, 64l+64) of each
-// round, the last round ending at Wend), append the tail bytes and the extra
-// byte; returns ~state (the crc32c::Extend value), wave-uniform.
-__device__ __forceinline__ uint32_t stream_finish(const uint32_t* __restrict__ L, uint32_t lb,
-                                                  uint32_t lane, const Blk& c, uint32_t s,
-                                                  uint32_t t0, bool has_extra) {
-  // levels 0..3 inside 16-lane rows: lane i (low k+1 bits set) takes lane
-  // i-2^k (DPP row_shr) and shifts it over its own 2^k segments
-  s = tree_level<0>(L, lane, s);
-  s = tree_level<1>(L, lane, s);
-  s = tree_level<2>(L, lane, s);
-  s = tree_level<3>(L, lane, s);
-  // levels 4..5 on the row results (wave-uniform: broadcast LDS reads)
-  const uint32_t g0 = readlane32(s, 15);
-  const uint32_t g1 = readlane32(s, 31);
-  const uint32_t g2 = readlane32(s, 47);
-  const uint32_t g3 = readlane32(s, 63);
-  const uint32_t t01 = crc_shift(L, kOffTree + 1024u * 4, g0) ^ g1;
-  const uint32_t t23 = crc_shift(L, kOffTree + 1024u * 4, g2) ^ g3;
-  uint32_t st = crc_shift(L, kOffTree + 1024u * 5, t01) ^ t23;
-  uint32_t t = t0;
-  for (uint32_t q = 0; q < c.nt; ++q) {
-    st = crc_byte(L, lb, st, t & 0xffu);
-    t >>= 8;
-  }
-  if (has_extra) st = crc_byte(L, lb, st, c.extra);
-  return ~st;
-}
-
-template <int MODE>
-__global__ void __launch_bounds__(kThreads) crc32c_stream_kernel(BlockArgs a) {
-  __shared__ uint32_t L[kLdsDwordsStream];
-  fill_tables(L);
-  fill_tinv(L);
-  const uint32_t lane = threadIdx.x & 63;
-  const uint32_t wave = uniform(threadIdx.x >> 6);
-  const uint32_t lb = (lane & 31) << 2;
-  const uint64_t nw = static_cast<uint64_t>(gridDim.x) * kWaves;
-  const uint64_t gw = static_cast<uint64_t>(blockIdx.x) * kWaves + wave;
-  uint64_t kbeg, kend;
-  wave_share(a.n, nw, gw, kbeg, kend);
-  if (kbeg >= kend) return;
-  const bool has_extra = (MODE == kModeCompute || MODE == kModeTrailer) && a.last_bytes;
-
-  // S0 for init = 0 (every block mode): ~0 moved back over m = 0..3 bytes
-  uint32_t kS0[4];
-  kS0[0] = 0xffffffffu;
-#pragma unroll
-  for (int m = 1; m < 4; ++m) kS0[m] = uniform(crc_unstep(L, lb, kS0[m - 1]));
-
-  DescBatch cb, nb;
-  uint64_t kb = kbeg;
-  load_batch<MODE>(a, kb, kend, lane, cb);
-  load_batch<MODE>(a, kb + kBatch, kend, lane, nb);
-  uint64_t k = kbeg;
-  Blk C = blk_setup<MODE>(a, L, lb, k, kend, kb, cb, nb, kS0);
-  Blk N = blk_setup<MODE>(a, L, lb, k + 1, kend, kb, cb, nb, kS0);
-  uint32_t rOut = 0, rSt = 0, rOk = 0;
-  StepBuf X, Y;
-  issue_step(a.base, lane, C.w0, C.we, C.LA, C.t0, C.t1, 0, X);
-  uint32_t r = 0, s = 0;
-
-  auto flush = [&](uint32_t cnt) {
-    const uint64_t i = kb + lane;
-    const bool mine = lane < cnt;
-    if (mine && a.out32) a.out32[i] = rOut;
-    if (MODE == kModeVerify) {
-      if (mine && a.stored_out) a.stored_out[i] = rSt;
-      if (mine && a.ok_out) a.ok_out[i] = static_cast<uint8_t>(rOk);
-      const uint64_t badm = __ballot(mine && rOk == 0);
-      if (a.mismatches && badm && lane == 0)
-        atomicAdd(a.mismatches, static_cast<unsigned long long>(__popcll(badm)));
-    }
-    if (MODE == kModeTrailer) {
-      if (mine && rOk) {
-        const uint64_t off = (static_cast<uint64_t>(cb.off_hi) << 32) | cb.off_lo;
-        uint8_t* p = a.base_w + off + cb.size;
-        if (a.last_bytes) p[0] = static_cast<uint8_t>(cb.extra);
-        stu32_bytes(p + 1, rOut);
-      }
-    }
-  };
-
-  // one step: issue (next) into nx, compute (C, r) from cu; false when done
-  auto step = [&](StepBuf& cu, StepBuf& nx) -> bool {
-    const bool last = C.slow || r + 1 >= C.R;
-    issue_step(a.base, lane, last ? N.w0 : C.w0, last ? N.we : C.we, last ? N.LA : C.LA,
-               last ? N.t0 : C.t0, last ? N.t1 : C.t1, last ? 0u : r + 1, nx);
-    if (!C.slow) s = stream_round(L, lb, lane, C, r, s, cu.w);
-    if (!last) {
-      ++r;
-      return true;
-    }
-    uint32_t crc = 0, stored = 0;
-    if (!C.slow) {
-      crc = stream_finish(L, lb, lane, C, s, cu.t0, has_extra);
-      if (MODE == kModeVerify)
-        stored = C.nt ? __builtin_amdgcn_alignbyte(cu.t1, cu.t0, C.nt) : cu.t0;
-    } else if (C.valid) {
-      const uint8_t* p = a.base + C.off;
-      const uint32_t init = MODE == kModeRaw ? C.extra : 0u;
-      crc = wave_crc32c(L, lane, lb, p, C.len, init, has_extra ? 1u : 0u, C.extra,
-                        reinterpret_cast<uint64_t>(a.base));
-      // retire() waits for the load INSIDE this branch: a pending load
-      // merging into the fast path would make hipcc drain the prefetch
-      // (s_waitcnt vmcnt(0)) at every block end.
-      if (MODE == kModeVerify) stored = retire(ldu32(p + C.size + 1));
-      crc = retire(crc);
-    }
-    uint32_t out, st = 0, ok = C.valid ? 1u : 0u;
-    if (MODE == kModeRaw) {
-      out = crc;
-    } else if (MODE == kModeVerify) {
-      const uint32_t computed = crc_mask(crc);  // reader_common.cc:36-47
-      st = stored - C.mod;
-      ok = (C.valid && st == computed) ? 1u : 0u;
-      out = computed;
-    } else {
-      out = crc_mask(crc) + C.mod;  // format.cc:594-600 + builder.cc:1340-1345
-    }
-    if (!C.valid) {
-      out = 0;
-      st = 0;
-    }
-    const uint32_t kk = static_cast<uint32_t>(k - kb);
-    rOut = lane == kk ? out : rOut;
-    rSt = lane == kk ? st : rSt;
-    rOk = lane == kk ? ok : rOk;
-    ++k;
-    if (k - kb == kBatch || k == kend) {
-      flush(static_cast<uint32_t>(k - kb));
-      if (k == kend) return false;
-      kb = k;
-      cb = nb;
-      load_batch<MODE>(a, kb + kBatch, kend, lane, nb);
-    }
-    C = N;
-    N = blk_setup<MODE>(a, L, lb, k + 1, kend, kb, cb, nb, kS0);
-    r = 0;
-    return true;
-  };
-  while (step(X, Y) && step(Y, X)) {
-  }
-}
-#endif  // FORST_DIAG
 
 // ---------------------------------------------------------------------------
 // Streaming block kernel v2: two independent CRC chains per lane.
@@ -972,10 +657,10 @@ __device__ __forceinline__ uint32_t small_crc2(const uint8_t* __restrict__ Lb, c
   return ~s;
 }
 
-// PROBE = 1 (diagnostics build only, FORST_CRC_VARIANT=probe_load): the same
-// loads and control flow, but every data word is only XOR-folded (no table
-// lookups) and every block reports ok -- the memory-side ceiling of this
-// access pattern; 2 = no finish, 3 = no head handling.
+// PROBE is always 0.  The parameter and the two probe arms of the round
+// dispatch below are what is left of the removed load-probe variants: without
+// those (never taken) arms the compiler orders one instruction of every
+// crc32c_stream2_kernel differently, and this kernel's code is to stay as it is.
 template <int MODE, int PROBE>
 __device__ __forceinline__ void crc32c_stream2_body(const BlockArgs& a) {
   __shared__ uint32_t L[kLds2Bytes / 4];
@@ -1061,19 +746,7 @@ __device__ __forceinline__ void crc32c_stream2_body(const BlockArgs& a) {
     }
     if (last) {
       uint32_t crc = 0, stored = 0;
-      if (PROBE == 2 || PROBE == 3) {  // rounds only / no head: finish cost still in 3
-        const uint32_t f = PROBE == 3
-                               ? stream_finish2<MODE>(Lb, K, lane, C, s, cu.t0, cu.t2, has_extra)
-                                      : s[0] ^ s[1];
-        stored = crc_mask(0) + C.mod;
-        crc = __ballot(f == 0x9e3779b9u) ? 1u : 0u;
-        s[0] = s[1] = 0;
-      } else if (PROBE) {
-        const uint32_t f = s[0] ^ s[1] ^ cu.t0 ^ cu.t1;
-        stored = crc_mask(0) + C.mod;
-        crc = __ballot(f == 0x9e3779b9u) ? 1u : 0u;
-        s[0] = s[1] = 0;
-      } else if (!C.slow()) {
+      if (!C.slow()) {
         crc = stream_finish2<MODE>(Lb, K, lane, C, s, cu.t0, cu.t2, has_extra);
         if (MODE == kModeVerify)
           stored = C.nt() ? __builtin_amdgcn_alignbyte(cu.t1, cu.t0, C.nt()) : cu.t0;
@@ -1132,13 +805,6 @@ __global__ void __launch_bounds__(kThreads) crc32c_stream2_kernel(BlockArgs a) {
   crc32c_stream2_body<MODE, 0>(a);
 }
 
-#ifdef FORST_DIAG
-template <int PROBE>
-__global__ void __launch_bounds__(kThreads) crc32c_stream2_probe_kernel(BlockArgs a) {
-  crc32c_stream2_body<kModeVerify, PROBE>(a);
-}
-#endif
-
 // ---------------------------------------------------------------------------
 // CRC32C rows kernel (v3): one block per 16-lane row.
 //
@@ -1161,12 +827,9 @@ __global__ void __launch_bounds__(kThreads) crc32c_stream2_probe_kernel(BlockArg
 // LDS: [0, 64K) G and J3 interleaved as in the v2 kernel, [64K, 124K) A[1..15],
 // [124K, 128K) B[1].
 // ---------------------------------------------------------------------------
-// verify results staged in LDS and stored after the loop (1), or stored as
-// rows finish (0): result stores in the streaming loop cost C2 verify 4.7 %
-// (stores share vmcnt with the loads; profiles/ab_r04/c2_verify_stores.log)
-#ifndef FORST_ROWS_STAGE
-#define FORST_ROWS_STAGE 1
-#endif
+// block-mode results are staged in LDS and stored after the loop, not as rows
+// finish: result stores in the streaming loop cost C2 verify 4.7 % (stores
+// share vmcnt with the loads; profiles/ab_r04/c2_verify_stores.log)
 constexpr uint32_t kStageW = 6144;  // results per workgroup (30 KiB of LDS)
 constexpr uint32_t kRowRound = 1024;
 constexpr uint32_t kRowChain = 512;
@@ -1308,27 +971,10 @@ struct CRStep {
   uint32_t t0, t1, t2, mod, extra;  // t2: the extra window dword (xtra)
 };
 
-template <int MODE, int PROBE = 0>
+template <int MODE>
 __device__ __forceinline__ void crow_issue(const BlockArgs& a, uint32_t lane, const CRowPos& P,
                                            uint64_t kbeg, CRStep& d) {
   const uint32_t t = lane & 15;
-  if (PROBE == 3) {  // diagnostics: the same bytes as 16-B aligned, row-contiguous pieces
-    const int64_t rb = (P.rp() & ~int64_t(15)) + 16 * t;
-#pragma unroll
-    for (uint32_t c = 0; c < 2; ++c)
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        int64_t so = rb + 256 * (2 * c + q);
-        so = so < 0 ? 0 : so;
-        const u32x4a4 v = ld16_a4(a.base + so);
-        d.w[c][4 * q + 0] = v.x;
-        d.w[c][4 * q + 1] = v.y;
-        d.w[c][4 * q + 2] = v.z;
-        d.w[c][4 * q + 3] = v.w;
-      }
-    d.t0 = d.t1 = d.t2 = d.mod = d.extra = 0u;
-    return;
-  }
   // the lane's chain-0 segment; chain 1 is 512 bytes on.  Round-0 segments
   // in front of the head hold no message byte: they are loaded from where
   // they are and discarded by the head reset; only a segment in front of the
@@ -1381,27 +1027,13 @@ __device__ __forceinline__ void crow_issue(const BlockArgs& a, uint32_t lane, co
     d.extra = 0u;
 }
 
-// PROBE (diagnostics build only): 1 = same loads and row bookkeeping, no
-// table work and no finish; 2 = no per-block finish.
-// DEPTH 2 (diagnostics build only): two steps of loads in flight per wave
-// (three step buffers, 12-wave workgroups at 3 waves/SIMD) instead of one.
-constexpr uint32_t kRowsD2Waves = 12;
-#ifdef FORST_DIAG
-// diagnostics build only: per-wave start / end wall clock (100 MHz) of the
-// last rows-kernel launch, for the tail analysis (tools/wave_tail.py)
-constexpr uint32_t kDiagWaves = 8192;
-__device__ unsigned long long g_wave_t0[kDiagWaves], g_wave_t1[kDiagWaves];
-#endif
 // Raw batches split by message length (FILT): messages shorter than
 // kRawSplit bytes go to crc32c_raw_lane_kernel (one message per lane), the
 // rest to the rows kernel, which drops the short ones from each descriptor
 // batch as it loads it.  A short WAL record still costs a row a whole 1 KiB
 // round; on C5 the records <= 512 B (40 % of them, 1.5 % of the bytes) took
 // 0.69 ms of the 9.03 ms raw pass (profiles/ab_r04/c5_record_classes_raw_crc.json).
-#ifndef FORST_RAW_SPLIT
-#define FORST_RAW_SPLIT 256
-#endif
-constexpr uint32_t kRawSplit = FORST_RAW_SPLIT;
+constexpr uint32_t kRawSplit = 256;
 
 // A message goes to the rows filter kernel when it has kRawSplit bytes or
 // more and its offset is below 2^58 (any larger one lies outside every
@@ -1410,15 +1042,12 @@ __device__ __forceinline__ bool raw_long(uint64_t off, uint32_t size) {
   return size >= kRawSplit && (off >> 58) == 0;
 }
 
-#ifndef FORST_RAW_RING
-#define FORST_RAW_RING 1
-#endif
-template <int MODE, int PROBE, int DEPTH, bool RAW_WG = false, bool FILT = false>
+template <int MODE, bool RAW_WG = false, bool FILT = false>
 __device__ __forceinline__ void crc32c_rows_body(const BlockArgs& a) {
   static_assert(!FILT || (MODE == kModeRaw && !RAW_WG), "length split: raw global feed only");
   __shared__ uint32_t L[kLds3Bytes / 4];
   feed_init();
-  fill_tables3<64 * (DEPTH == 2 ? kRowsD2Waves : kWaves)>(L);
+  fill_tables3<kThreads>(L);
   const uint8_t* Lb = reinterpret_cast<const uint8_t*>(L);
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t wave = uniform(threadIdx.x >> 6);
@@ -1427,18 +1056,12 @@ __device__ __forceinline__ void crc32c_rows_body(const BlockArgs& a) {
   __shared__ uint32_t s0t[4];  // head states by start alignment (a select, not branches)
   if (threadIdx.x < 4) s0t[threadIdx.x] = kCrcS0[threadIdx.x];
   __syncthreads();
-  const uint64_t nw = static_cast<uint64_t>(gridDim.x) * (DEPTH == 2 ? kRowsD2Waves : kWaves);
-  const uint64_t gw = static_cast<uint64_t>(blockIdx.x) * (DEPTH == 2 ? kRowsD2Waves : kWaves) + wave;
+  const uint64_t nw = static_cast<uint64_t>(gridDim.x) * kWaves;
+  const uint64_t gw = static_cast<uint64_t>(blockIdx.x) * kWaves + wave;
   const bool has_extra = (MODE == kModeCompute || MODE == kModeTrailer) && a.last_bytes;
 
   // descriptor batches from the work feed: lane j <-> descriptor cg + j (cb),
   // ng + j (nb); a row's rel is the descriptor's global index (n < 2^32 - 1)
-#ifdef FORST_DIAG
-  if (lane == 0 && gw < kDiagWaves) {
-    g_wave_t0[gw] = wall_clock64();
-    g_wave_t1[gw] = 0;
-  }
-#endif
   BatchFeed feed;
   // block modes: the workgroup feed in 4-descriptor batches (one block per
   // row; A/B against 8: C2 verify +2.2 %, write +1.8 %, NS16 +0.9 %, C4
@@ -1451,14 +1074,13 @@ __device__ __forceinline__ void crc32c_rows_body(const BlockArgs& a) {
   uint64_t cg = feed_first<kWgFeed, kChunk>(a, nw, gw, lane, feed);
   // verify: results staged in LDS, stored after the loop by the whole
   // workgroup (so every wave reaches the end: no early return)
-  constexpr bool kStage = FORST_ROWS_STAGE && MODE != kModeRaw && kWgFeed && DEPTH == 1 &&
-                          PROBE == 0;
+  constexpr bool kStage = MODE != kModeRaw;
   __shared__ uint32_t st_out[kStage ? kStageW : 1];
   __shared__ uint8_t st_ok[kStage ? kStageW : 4];
   // raw mode: each wave's results collected in an LDS ring and stored 64 per
   // instruction when it fills and after the loop (stores share vmcnt with the
   // loads, so a store per finishing row delayed the next step's data)
-  constexpr bool kRing = FORST_RAW_RING && MODE == kModeRaw && PROBE == 0 && DEPTH == 1;
+  constexpr bool kRing = MODE == kModeRaw;
   constexpr uint32_t kRingN = 224;  // per wave (16 waves: 28 KiB beside the 128 KiB of tables)
   __shared__ uint32_t ring_i[kRing ? kWaves * kRingN : 1], ring_v[kRing ? kWaves * kRingN : 1];
   uint32_t* const ri = ring_i + (kRing ? wave * kRingN : 0);
@@ -1587,26 +1209,23 @@ __device__ __forceinline__ void crc32c_rows_body(const BlockArgs& a) {
       }
     }
   };
-  CRowPos I, I2;
+  CRowPos I;
   advance(C, I);
-  if (DEPTH == 2) advance(I, I2);
-  CRStep X, Y, Z;
-  crow_issue<MODE, PROBE>(a, lane, C, kbeg, X);
-  if (DEPTH == 2) crow_issue<MODE, PROBE>(a, lane, I, kbeg, Y);
+  CRStep X, Y;
+  crow_issue<MODE>(a, lane, C, kbeg, X);
   uint32_t s[2] = {0, 0};
 
   // cu: the current step's data (ready); nx: the buffer that receives the
-  // loads issued now (the position DEPTH steps ahead)
+  // loads issued now (the position one step ahead)
   auto step = [&](CRStep& cu, CRStep& nx) -> bool {
-
     // raw mode (WAL records, mixed sizes): no early return (see
     // xxh3_frag_kernel), both step copies issue on every path round the loop
     // and the next step's loads overlap this step's wait (C5 verify / writer
     // +1.5 %); the block modes keep the early exit, which measured better on
     // uniform blocks (A/B on one box: C2 0.600 vs 0.592)
     const bool live = __ballot(C.rel != kNoBlk || (FILT && C.wait())) != 0;
-    if ((DEPTH == 2 || MODE != kModeRaw) && !live) return false;
-    crow_issue<MODE, PROBE>(a, lane, DEPTH == 2 ? I2 : I, kbeg, nx);
+    if (MODE != kModeRaw && !live) return false;
+    crow_issue<MODE>(a, lane, I, kbeg, nx);
     const bool fast = C.rel != kNoBlk && !C.slow();
     const bool r0 = C.r0();
     // ---- one 1 KiB round of every row ----
@@ -1617,16 +1236,8 @@ __device__ __forceinline__ void crc32c_rows_body(const BlockArgs& a) {
     // message, plus the initial state moved back over them), which discards
     // whatever the words in front of it added.  Steps without a row at
     // round 0 run the plain chains.
-    const bool head = PROBE == 0 && __ballot(fast && r0);
-    if (PROBE == 1 || PROBE == 3) {
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        uint32_t x = r0 ? 0u : s[c];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) x ^= cu.w[c][j];
-        s[c] = x;
-      }
-    } else if (!head) {
+    const bool head = __ballot(fast && r0);
+    if (!head) {
 #pragma unroll
       for (int c = 0; c < 2; ++c) {
         uint32_t lj[4], lg[4];
@@ -1681,8 +1292,7 @@ __device__ __forceinline__ void crc32c_rows_body(const BlockArgs& a) {
     }
     // ---- rows that finish a block in this step ----
     const bool fin = C.rel != kNoBlk && (C.slow() || C.rl <= 1);
-    if (PROBE != 0 && fin && t == 15 && a.out32) a.out32[C.rel] = s[0] ^ s[1] ^ cu.t0;
-    if (PROBE == 0 && __ballot(fin)) {
+    if (__ballot(fin)) {
       // chain states to the row end (A[15 - t]), row XOR, chain 0 over chain 1
       const bool lo0 = t == 15;
       const uint32_t abase = kOffA2 + 4096 * (14 - t);
@@ -1732,9 +1342,6 @@ __device__ __forceinline__ void crc32c_rows_body(const BlockArgs& a) {
         // later step wait for them (C5 writer 9.19 -> 9.90 ms)
         const uint32_t v = a.wal_hs ? crc_mask(crc) : crc;
         const bool differs = !a.expect || !valid || v != cu.mod;
-#ifdef FORST_RAW_STORE_PROBE  // timing only: the store path kept but (almost) never taken
-        if (mine && differs && a.out32 && v == 0x9e3779b9u) a.out32[i] = valid ? v : 0u;
-#else
         if constexpr (kRing) {
           const bool put = mine && differs && a.out32 != nullptr;
           const uint64_t pm = __ballot(put);
@@ -1748,10 +1355,7 @@ __device__ __forceinline__ void crc32c_rows_body(const BlockArgs& a) {
             rcount += static_cast<uint32_t>(__popcll(pm));
             if (rcount > kRingN - 64) ring_flush();
           }
-        } else {
-          if (mine && differs && a.out32) a.out32[i] = valid ? v : 0u;
         }
-#endif
       } else if (MODE == kModeVerify) {
         const uint32_t computed = crc_mask(crc);  // reader_common.cc:36-47
         const uint32_t st = stored - cu.mod;
@@ -1803,31 +1407,18 @@ __device__ __forceinline__ void crc32c_rows_body(const BlockArgs& a) {
     asm volatile("" ::"v"(cu.t0), "v"(cu.t1), "v"(cu.t2), "v"(cu.mod), "v"(cu.extra));
 #endif
     C = I;
-    if (DEPTH == 2) {
-      I = I2;
-      advance(I, I2);
-    } else {
-      advance(C, I);
-    }
+    advance(C, I);
     return live;
   };
-  if (DEPTH == 2) {
-    while (step(X, Z) && step(Y, X) && step(Z, Y)) {
+  if (MODE == kModeRaw) {
+    for (bool more = true; more;) {
+      step(X, Y);
+      more = step(Y, X);
     }
   } else {
-    if (MODE == kModeRaw) {
-      for (bool more = true; more;) {
-        step(X, Y);
-        more = step(Y, X);
-      }
-    } else {
-      while (step(X, Y) && step(Y, X)) {
-      }
+    while (step(X, Y) && step(Y, X)) {
     }
   }
-#ifdef FORST_DIAG
-  if (lane == 0 && gw < kDiagWaves) g_wave_t1[gw] = wall_clock64();
-#endif
   if constexpr (kRing) {
     if (rcount) ring_flush();
   }
@@ -1864,7 +1455,7 @@ __device__ __forceinline__ void crc32c_rows_body(const BlockArgs& a) {
 
 template <int MODE>
 __global__ void __launch_bounds__(kThreads) crc32c_rows_kernel(BlockArgs a) {
-  crc32c_rows_body<MODE, 0, 1>(a);
+  crc32c_rows_body<MODE>(a);
 }
 // raw batches smaller than one 64-descriptor chunk per wave of the grid (the
 // records a WAL recovery's fused kernel does not cover, a WAL write of a few
@@ -1872,11 +1463,11 @@ __global__ void __launch_bounds__(kThreads) crc32c_rows_kernel(BlockArgs a) {
 // chunks, 64 records one after another on each, while the workgroup feed
 // spreads them over every wave in 4-descriptor batches
 __global__ void __launch_bounds__(kThreads) crc32c_rows_raw_small_kernel(BlockArgs a) {
-  crc32c_rows_body<kModeRaw, 0, 1, true>(a);
+  crc32c_rows_body<kModeRaw, true>(a);
 }
 // the long messages of a raw batch (kRawSplit bytes or more)
 __global__ void __launch_bounds__(kThreads) crc32c_rows_raw_filt_kernel(BlockArgs a) {
-  crc32c_rows_body<kModeRaw, 0, 1, false, true>(a);
+  crc32c_rows_body<kModeRaw, false, true>(a);
 }
 
 // ---- the short messages of a raw batch: one message per lane --------------
@@ -2028,75 +1619,6 @@ __global__ void __launch_bounds__(kLaneThreads) crc32c_raw_lane_kernel(BlockArgs
   }
 }
 
-#ifdef FORST_DIAG
-template <int PROBE>
-__global__ void __launch_bounds__(kThreads) crc32c_rows_probe_kernel(BlockArgs a) {
-  crc32c_rows_body<kModeVerify, PROBE, 1>(a);
-}
-template <int MODE>
-__global__ void __launch_bounds__(64 * kRowsD2Waves) crc32c_rows_d2_kernel(BlockArgs a) {
-  crc32c_rows_body<MODE, 0, 2>(a);
-}
-__global__ void __launch_bounds__(64 * kRowsD2Waves) crc32c_rows_d2_probe_kernel(BlockArgs a) {
-  crc32c_rows_body<kModeVerify, 1, 2>(a);
-}
-
-// Access-pattern probe (diagnostics only, FORST_CRC_VARIANT=pat<G>_<C>): no
-// CRC work, no work feed.  Groups of G lanes (16 = a row, 64 = the wave) walk
-// their blocks (static: group k of the grid takes blocks k, k + ngroups, ...)
-// in C-byte steps, one step of loads in flight ahead of an XOR of the
-// current one: the memory ceiling of "C contiguous bytes per group per step"
-// against the rows kernel's 1 KiB per row and the v2 kernel's 4 KiB per wave.
-// The plain streaming ceiling (diagnostics only, FORST_CRC_VARIANT=stream):
-// the whole buffer read once, every wave a contiguous 4 KiB per step (16 B
-// per lane, 4 loads per lane in flight), grid-stride, no descriptors.
-__global__ void __launch_bounds__(kThreads) crc32c_stream_probe_kernel(BlockArgs a) {
-  const uint64_t nthr = static_cast<uint64_t>(gridDim.x) * kThreads;
-  const uint64_t n16 = a.base_len / 16;
-  uint32_t acc = 0;
-  for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kThreads + threadIdx.x; i < n16;
-       i += 4 * nthr) {
-    u32x4a4 v[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const uint64_t j = i + k * nthr;
-      v[k] = ld16_a4(a.base + 16 * (j < n16 ? j : i));
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) acc ^= v[k].x ^ v[k].y ^ v[k].z ^ v[k].w;
-  }
-  if (a.out32 && threadIdx.x == 0) a.out32[blockIdx.x] = acc;
-}
-
-template <int G, int C>
-__global__ void __launch_bounds__(kThreads) crc32c_pattern_probe_kernel(BlockArgs a) {
-  constexpr int kPer = C / G / 16;  // 16-byte loads per lane per step
-  const uint32_t lane = threadIdx.x & 63;
-  const uint32_t gl = lane % G;
-  const uint64_t ng = static_cast<uint64_t>(gridDim.x) * (kThreads / G);
-  const uint64_t g0 = static_cast<uint64_t>(blockIdx.x) * (kThreads / G) + threadIdx.x / G;
-  uint32_t acc = 0;
-  for (uint64_t b = g0; b < a.n; b += ng) {
-    const uint64_t off = a.offsets[b] & ~15ull;
-    const uint32_t sz = a.sizes[b];
-    const uint32_t steps = (sz + 16 + C - 1) / C;
-    u32x4a4 cur[kPer], nxt[kPer];
-#pragma unroll
-    for (int k = 0; k < kPer; ++k) cur[k] = ld16_a4(a.base + off + 16 * (gl + G * k));
-    for (uint32_t st = 0; st < steps; ++st) {
-      const uint64_t o2 = off + static_cast<uint64_t>(st + 1 < steps ? st + 1 : st) * C;
-#pragma unroll
-      for (int k = 0; k < kPer; ++k) nxt[k] = ld16_a4(a.base + o2 + 16 * (gl + G * k));
-#pragma unroll
-      for (int k = 0; k < kPer; ++k) acc ^= cur[k].x ^ cur[k].y ^ cur[k].z ^ cur[k].w;
-#pragma unroll
-      for (int k = 0; k < kPer; ++k) cur[k] = nxt[k];
-    }
-    if (gl == 0 && a.out32) a.out32[b] = acc;
-  }
-}
-#endif
-
 // One wave per block, no streaming: serves buffers shorter than one 4 KiB
 // round (the streaming kernels' dummy loads need that much).
 template <int MODE>
@@ -2172,10 +1694,6 @@ enum class CrcKernel {
   kSimple,  // one wave per block: buffers shorter than one 4 KiB round
   kRows,    // one block per 16-lane row (crc32c_rows_kernel)
   kV2,      // one block per wave, two chains per lane (crc32c_stream2_kernel)
-#ifdef FORST_DIAG
-  kV1, kRowsD2, kRowsProbeLoad, kRowsProbeNoFin, kRowsD2ProbeLoad, kRowsProbeContig, kV2ProbeLoad, kV2ProbeRounds, kV2ProbeNoHead,
-  kPat16_1k, kPat16_2k, kPat16_4k, kPat64_4k, kStream,
-#endif
 };
 
 hipError_t launch_kernel(void (*k)(BlockArgs), uint32_t grid, uint32_t threads, BlockArgs a,
@@ -2202,30 +1720,7 @@ const char* crc_kernel_name(CrcKernel k, int mode) {
        "crc32c_rows_kernel<raw>"},
       {"crc32c_stream2_kernel<compute>", "crc32c_stream2_kernel<trailer>",
        "crc32c_stream2_kernel<verify>", "crc32c_stream2_kernel<raw>"},
-#ifdef FORST_DIAG
-      {"crc32c_stream_kernel<compute>", "crc32c_stream_kernel<trailer>",
-       "crc32c_stream_kernel<verify>", "crc32c_stream_kernel<raw>"},
-      {"crc32c_rows_d2_kernel<compute>", "crc32c_rows_d2_kernel<trailer>",
-       "crc32c_rows_d2_kernel<verify>", "crc32c_rows_d2_kernel<raw>"},
-#endif
   };
-#ifdef FORST_DIAG
-  switch (k) {
-    case CrcKernel::kRowsProbeLoad: return "crc32c_rows_probe_kernel<1>";
-    case CrcKernel::kRowsProbeNoFin: return "crc32c_rows_probe_kernel<2>";
-    case CrcKernel::kRowsD2ProbeLoad: return "crc32c_rows_d2_probe_kernel";
-    case CrcKernel::kRowsProbeContig: return "crc32c_rows_probe_kernel<3>";
-    case CrcKernel::kPat16_1k: return "crc32c_pattern_probe_kernel<16,1024>";
-    case CrcKernel::kPat16_2k: return "crc32c_pattern_probe_kernel<16,2048>";
-    case CrcKernel::kPat16_4k: return "crc32c_pattern_probe_kernel<16,4096>";
-    case CrcKernel::kPat64_4k: return "crc32c_pattern_probe_kernel<64,4096>";
-    case CrcKernel::kStream: return "crc32c_stream_probe_kernel";
-    case CrcKernel::kV2ProbeLoad: return "crc32c_stream2_probe_kernel<1>";
-    case CrcKernel::kV2ProbeRounds: return "crc32c_stream2_probe_kernel<2>";
-    case CrcKernel::kV2ProbeNoHead: return "crc32c_stream2_probe_kernel<3>";
-    default: break;
-  }
-#endif
   return kNames[static_cast<int>(k)][mode & 3];
 }
 
@@ -2239,88 +1734,26 @@ hipError_t launch_crc_mode(CrcKernel k, const BlockArgs& a, uint32_t grid, hipSt
       return launch_kernel(crc32c_block_kernel_simple<M>, grid, kThreads, a, s);
     case CrcKernel::kRows:
       // block modes: the workgroup feed (stream_common.h), no ticket counter
-      if (M != kModeRaw) {
+      // (if constexpr: raw batches never launch crc32c_rows_kernel<raw>, so it
+      // is not instantiated)
+      if constexpr (M != kModeRaw) {
         BlockArgs b = a;
         b.wg_cost = FORST_CRC_BLOCK_COST;  // (stream_common.h wg_range)
         return launch_kernel(crc32c_rows_kernel<M>, grid, 64 * kWaves, b, s);
-      }
-      if (a.n < uint64_t(64) * grid * kWaves)
-        return launch_kernel(crc32c_rows_raw_small_kernel, grid, 64 * kWaves, a, s);
-      if constexpr (M == kModeRaw && kRawSplit > 0) {
+      } else {
+        if (a.n < uint64_t(64) * grid * kWaves)
+          return launch_kernel(crc32c_rows_raw_small_kernel, grid, 64 * kWaves, a, s);
         // short messages one per lane, then the rows kernel over the rest
         const hipError_t e = launch_kernel(crc32c_raw_lane_kernel, 2 * device_info().num_cus,
                                            kLaneThreads, a, s);
         if (e != hipSuccess) return e;
         return launch_fed(crc32c_rows_raw_filt_kernel, grid, kWaves, a, s);
       }
-      return launch_fed(crc32c_rows_kernel<M>, grid, kWaves, a, s);
     case CrcKernel::kV2:
       return launch_kernel(crc32c_stream2_kernel<M>, grid, kThreads, a, s);
-#ifdef FORST_DIAG
-    case CrcKernel::kV1:
-      return launch_kernel(crc32c_stream_kernel<M>, grid, kThreads, a, s);
-    case CrcKernel::kRowsD2:
-      return launch_fed(crc32c_rows_d2_kernel<M>, grid, kRowsD2Waves, a, s);
-    case CrcKernel::kRowsProbeLoad:
-      return launch_fed(crc32c_rows_probe_kernel<1>, grid, kWaves, a, s);
-    case CrcKernel::kRowsProbeNoFin:
-      return launch_fed(crc32c_rows_probe_kernel<2>, grid, kWaves, a, s);
-    case CrcKernel::kRowsD2ProbeLoad:
-      return launch_fed(crc32c_rows_d2_probe_kernel, grid, kRowsD2Waves, a, s);
-    case CrcKernel::kRowsProbeContig:
-      return launch_fed(crc32c_rows_probe_kernel<3>, grid, kWaves, a, s);
-    case CrcKernel::kPat16_1k:
-      hipLaunchKernelGGL((crc32c_pattern_probe_kernel<16, 1024>), dim3(grid), dim3(kThreads), 0, s, a);
-      return hipGetLastError();
-    case CrcKernel::kPat16_2k:
-      hipLaunchKernelGGL((crc32c_pattern_probe_kernel<16, 2048>), dim3(grid), dim3(kThreads), 0, s, a);
-      return hipGetLastError();
-    case CrcKernel::kPat16_4k:
-      hipLaunchKernelGGL((crc32c_pattern_probe_kernel<16, 4096>), dim3(grid), dim3(kThreads), 0, s, a);
-      return hipGetLastError();
-    case CrcKernel::kPat64_4k:
-      hipLaunchKernelGGL((crc32c_pattern_probe_kernel<64, 4096>), dim3(grid), dim3(kThreads), 0, s, a);
-      return hipGetLastError();
-    case CrcKernel::kStream:
-      hipLaunchKernelGGL(crc32c_stream_probe_kernel, dim3(4 * grid), dim3(kThreads), 0, s, a);
-      return hipGetLastError();
-    case CrcKernel::kV2ProbeLoad:
-      return launch_kernel(crc32c_stream2_probe_kernel<1>, grid, kThreads, a, s);
-    case CrcKernel::kV2ProbeRounds:
-      return launch_kernel(crc32c_stream2_probe_kernel<2>, grid, kThreads, a, s);
-    case CrcKernel::kV2ProbeNoHead:
-      return launch_kernel(crc32c_stream2_probe_kernel<3>, grid, kThreads, a, s);
-#endif
   }
   return hipErrorInvalidValue;
 }
-
-#ifdef FORST_DIAG
-// diagnostics build: FORST_CRC_VARIANT overrides the kernel choice (probe
-// variants only replace verify launches; their results are not checksums)
-CrcKernel diag_crc_kernel(CrcKernel k, int mode) {
-  const std::string v = diag_env("FORST_CRC_VARIANT");
-  const bool vf = mode == kModeVerify;
-  if (v == "simple") return CrcKernel::kSimple;
-  if (v == "rows") return CrcKernel::kRows;
-  if (v == "v2") return CrcKernel::kV2;
-  if (v == "v1") return CrcKernel::kV1;
-  if (v == "rows_d2") return CrcKernel::kRowsD2;
-  if (v == "rows_probe_load" && vf) return CrcKernel::kRowsProbeLoad;
-  if (v == "rows_probe_nofin" && vf) return CrcKernel::kRowsProbeNoFin;
-  if (v == "rows_d2_probe_load" && vf) return CrcKernel::kRowsD2ProbeLoad;
-  if (v == "rows_probe_contig" && vf) return CrcKernel::kRowsProbeContig;
-  if (v == "pat16_1k" && vf) return CrcKernel::kPat16_1k;
-  if (v == "pat16_2k" && vf) return CrcKernel::kPat16_2k;
-  if (v == "pat16_4k" && vf) return CrcKernel::kPat16_4k;
-  if (v == "pat64_4k" && vf) return CrcKernel::kPat64_4k;
-  if (v == "stream" && vf) return CrcKernel::kStream;
-  if (v == "probe_load" && vf) return CrcKernel::kV2ProbeLoad;
-  if (v == "probe_rounds" && vf) return CrcKernel::kV2ProbeRounds;
-  if (v == "probe_nohead" && vf) return CrcKernel::kV2ProbeNoHead;
-  return k;
-}
-#endif
 
 }  // namespace
 
@@ -2328,7 +1761,6 @@ CrcKernel diag_crc_kernel(CrcKernel k, int mode) {
 // longer one would be left out: the caller guarantees the lengths)
 hipError_t launch_crc32c_raw_lanes(const BlockArgs& a, hipStream_t stream) {
   if (a.n == 0) return hipSuccess;
-  if (kRawSplit < 256) return hipErrorInvalidValue;
   return launch_kernel(crc32c_raw_lane_kernel, 2 * device_info().num_cus, kLaneThreads, a, stream);
 }
 
@@ -2361,21 +1793,13 @@ hipError_t launch_crc32c_blocks(int mode, const BlockArgs& a, hipStream_t stream
                 : (a.n < 0xffffffffull && (a.kernel_hint ? a.kernel_hint == 1 : true))
                     ? CrcKernel::kRows
                     : CrcKernel::kV2;
-#ifdef FORST_DIAG
-  // (never for the WAL writer mode: only the rows kernel masks its CRCs)
-  if (a.base_len >= kRB && !a.wal_hs) k = diag_crc_kernel(k, mode);
-  if (k == CrcKernel::kRows || k == CrcKernel::kRowsD2) {
-    if (a.n >= 0xffffffffull) k = CrcKernel::kV2;
-  }
-#endif
   // the WAL writer mode (wal_hs: header offsets + payload lengths, masked
   // output) exists in the rows kernel only
   if (a.wal_hs && (mode != kModeRaw || k != CrcKernel::kRows)) return hipErrorInvalidValue;
   *name = crc_kernel_name(k, mode);
   if (k == CrcKernel::kRows && mode == kModeRaw)
     *name = a.n < uint64_t(64) * grid * kWaves ? "crc32c_rows_raw_small_kernel"
-            : kRawSplit > 0                    ? "crc32c_rows_raw_filt_kernel"
-                                               : "crc32c_rows_kernel<raw>";
+                                               : "crc32c_rows_raw_filt_kernel";
   switch (mode) {
     case kModeCompute:
       return launch_crc_mode<kModeCompute>(k, a, grid, stream);
@@ -2388,149 +1812,7 @@ hipError_t launch_crc32c_blocks(int mode, const BlockArgs& a, hipStream_t stream
   }
 }
 
-#ifdef FORST_DIAG
-// ---------------------------------------------------------------------------
-// WAL, one wave per log block / record (diagnostics build only: A/B reference
-// of the wal.hip pipeline; db/log_reader.cc:450-531, db/log_writer.cc:228-263)
-// ---------------------------------------------------------------------------
-namespace {
-
-constexpr uint32_t kLogBlock = 32768;  // db/log_format.h:45
-constexpr uint32_t kLogHdr = 7;        // db/log_format.h:48
-constexpr uint32_t kLogRHdr = 11;      // db/log_format.h:52
-
-__device__ __forceinline__ bool is_recyclable_type(uint32_t t) {
-  return (t >= 5 && t <= 8) || t == 11;
-}
-
-// One wave per 32 KiB log block; headers are walked serially (their
-// positions depend on the previous length), each record's CRC is a
-// wave-parallel crc32c over header[6 .. hdr+len).
-__global__ void __launch_bounds__(kThreads) wal_verify_kernel(WalArgs a) {
-  __shared__ uint32_t L[kLdsDwords];
-  fill_tables(L);
-  const uint32_t lane = threadIdx.x & 63;
-  const uint32_t wave = uniform(threadIdx.x >> 6);
-  const uint32_t lb = (lane & 31) << 2;
-  const uint64_t lo = reinterpret_cast<uint64_t>(a.log);
-  const uint64_t nw = static_cast<uint64_t>(gridDim.x) * kWaves;
-  for (uint64_t bi = static_cast<uint64_t>(blockIdx.x) * kWaves + wave;
-       bi < a.n_blocks; bi += nw) {
-    const uint64_t b = a.first_block + bi;
-    const uint64_t start = b * kLogBlock;
-    uint64_t end = start + kLogBlock;
-    if (end > a.log_len) end = a.log_len;
-    uint32_t status = 0, nrec = 0;
-    uint64_t pos = start;
-    while (start < end && end - pos >= kLogHdr) {
-      const uint8_t* h = a.log + pos;
-      const uint32_t hdr_lo = ldu32(h + 3);  // bytes 3..6
-      const uint32_t length = (hdr_lo >> 8) & 0xffffu;
-      const uint32_t type = hdr_lo >> 24;
-      const bool recyc = is_recyclable_type(type);
-      const uint32_t hs = recyc ? kLogRHdr : kLogHdr;
-      if (end - pos < hs) break;  // truncated header at EOF (ReadMore)
-      if (hs + length > end - pos) {
-        status = 2;  // kBadRecordLen
-        break;
-      }
-      if (recyc && ldu32(h + 7) != a.log_number) {
-        status = 4;  // kOldRecord
-        break;
-      }
-      if (type == 0 && length == 0) {
-        status = 3;  // kZeroType: preallocated space, rest of block skipped
-        break;
-      }
-      const uint32_t expected = crc_unmask(ldu32(h));
-      const uint32_t actual =
-          wave_crc32c(L, lane, lb, h + 6, length + hs - 6, 0, 0, 0, lo);
-      if (actual != expected) {
-        status = 1;  // kBadRecordChecksum: rest of block dropped
-        break;
-      }
-      ++nrec;
-      pos += hs + length;
-    }
-    if (lane == 0) {
-      if (a.status_out) a.status_out[bi] = static_cast<uint8_t>(status);
-      if (a.nrec_out) a.nrec_out[bi] = nrec;
-      if (a.fail_off_out) a.fail_off_out[bi] = static_cast<uint32_t>(pos - start);
-      if (a.bad_blocks && status != 0 && status != 3) atomicAdd(a.bad_blocks, 1ull);
-    }
-  }
-}
-
-// EmitPhysicalRecord's CRC == Mask(Value(header[6 .. hs) || payload)).
-__global__ void __launch_bounds__(kThreads) wal_record_crc_kernel(WalArgs a) {
-  __shared__ uint32_t L[kLdsDwords];
-  fill_tables(L);
-  const uint32_t lane = threadIdx.x & 63;
-  const uint32_t wave = uniform(threadIdx.x >> 6);
-  const uint32_t lb = (lane & 31) << 2;
-  const uint64_t lo = reinterpret_cast<uint64_t>(a.log);
-  const uint64_t nw = static_cast<uint64_t>(gridDim.x) * kWaves;
-  for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kWaves + wave;
-       i < a.n_records; i += nw) {
-    const uint64_t off = a.header_offsets[i];
-    uint32_t c = 0;
-    bool inb = off <= a.log_len && a.log_len - off >= kLogHdr;
-    uint32_t length = 0, hs = kLogHdr;
-    if (inb) {
-      const uint8_t* h = a.log + off;
-      const uint32_t hdr_lo = ldu32(h + 3);
-      length = (hdr_lo >> 8) & 0xffffu;
-      hs = is_recyclable_type(hdr_lo >> 24) ? kLogRHdr : kLogHdr;
-      inb = a.log_len - off >= uint64_t(hs) + length;
-    }
-    if (inb) {
-      const uint8_t* h = a.log + off;
-      c = crc_mask(wave_crc32c(L, lane, lb, h + 6, length + hs - 6, 0, 0, 0, lo));
-      if (lane == 0 && a.write_in_place) stu32_bytes(a.log_w + off, c);
-    }
-    if (lane == 0 && a.crc_out) a.crc_out[i] = c;
-  }
-}
-
-}  // namespace
-
-hipError_t launch_wal_verify_wave(const WalArgs& a, hipStream_t stream,
-                             const char** name) {
-  const DeviceInfo& di = device_info();
-  if (a.n_blocks == 0) return hipSuccess;
-  uint32_t grid = static_cast<uint32_t>(
-      std::min<uint64_t>((a.n_blocks + kWaves - 1) / kWaves, di.num_cus));
-  *name = "wal_verify_kernel";
-  hipLaunchKernelGGL(wal_verify_kernel, dim3(grid), dim3(kThreads), 0, stream, a);
-  return hipGetLastError();
-}
-
-hipError_t launch_wal_record_crc_wave(const WalArgs& a, hipStream_t stream,
-                                 const char** name) {
-  const DeviceInfo& di = device_info();
-  if (a.n_records == 0) return hipSuccess;
-  uint32_t grid = static_cast<uint32_t>(
-      std::min<uint64_t>((a.n_records + kWaves - 1) / kWaves, di.num_cus));
-  *name = "wal_record_crc_kernel";
-  hipLaunchKernelGGL(wal_record_crc_kernel, dim3(grid), dim3(kThreads), 0,
-                     stream, a);
-  return hipGetLastError();
-}
-
-#endif  // FORST_DIAG
-
 }  // namespace forst
-
-#ifdef FORST_DIAG
-// diagnostics build only: per-wave start / end clocks of the last rows launch
-extern "C" __attribute__((visibility("default"))) int forst_diag_wave_times(
-    unsigned long long* t0, unsigned long long* t1, unsigned n) {
-  if (n > forst::kDiagWaves) n = forst::kDiagWaves;
-  if (hipMemcpyFromSymbol(t0, HIP_SYMBOL(forst::g_wave_t0), n * 8) != hipSuccess) return -3;
-  if (hipMemcpyFromSymbol(t1, HIP_SYMBOL(forst::g_wave_t1), n * 8) != hipSuccess) return -3;
-  return 0;
-}
-#endif
 
 #ifdef FORST_DEBUG_BOUNDS
 // diagnostics build only: first out-of-bounds access recorded by the CRC

@@ -93,17 +93,5 @@ __device__ __forceinline__ uint32_t row_ror_xor(uint32_t v) {
                                                                0xf, 0xf, false));
 }
 
-// bytes [a, b) of a 16-byte chunk kept (0 <= a <= b <= 16): the masks of its
-// two little-endian 64-bit halves
-__device__ __forceinline__ uint64_t keep64(uint32_t n) {  // low n bytes, n <= 8
-  return n >= 8 ? ~0ull : ((1ull << (8 * n)) - 1);
-}
-__device__ __forceinline__ void keep_mask(uint32_t a, uint32_t b, uint64_t& lo, uint64_t& hi) {
-  const uint32_t a0 = a < 8 ? a : 8, b0 = b < 8 ? b : 8;
-  const uint32_t a1 = a > 8 ? a - 8 : 0, b1 = b > 8 ? b - 8 : 0;
-  lo = keep64(b0) & ~keep64(a0);
-  hi = keep64(b1) & ~keep64(a1);
-}
-
 }  // namespace fcrc
 }  // namespace forst

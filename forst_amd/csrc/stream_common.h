@@ -39,7 +39,8 @@ __device__ __forceinline__ void wave_share(uint64_t n, uint64_t nw, uint64_t gw,
 // starting at nw * share1 + 64 * t, t claimed from a.ticket (one atomic per
 // chunk; a wave whose blocks ran long simply claims fewer chunks), or dealt
 // round-robin (t = gw, gw + nw, ...) when the launch has no ticket counter
-// (a.ticket points at 64 counters, [0] zeroed per launch).
+// (a.ticket points at 64 counters, [0] zeroed per launch; feed_setup gives
+// every global-feed launch one, so the round-robin deal is not taken today).
 // Chunks never straddle a batch, so a batch is one contiguous run
 // [g, g + 64) of descriptors (entries >= n are empty).  Once a batch starts
 // at >= n every later one does too and the feed stops claiming.
@@ -87,7 +88,7 @@ __device__ __forceinline__ uint64_t feed_claim_global(const BlockArgs& a, uint64
 // - The small grain lets the fast and slow waves of a SIMD finish together.
 //   The four waves of a SIMD progress at different rates (age-ordered), and
 //   the global feed's last 64-descriptor chunk left them idle for 7-13 % of a
-//   C2 launch (tools/wave_tail.py).
+//   C2 launch.
 // - Ranges by bytes, not by count (round 3): a batch sorted or clustered by
 //   block size (64 KiB blocks, then 4 KiB; an arena of SST files with
 //   different block sizes) would otherwise give some workgroups many times

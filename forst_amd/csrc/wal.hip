@@ -29,9 +29,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <cstdlib>
 #include <cstring>
-#include <string>
 
 #include "device_common.h"
 #include "engine.h"
@@ -39,11 +37,6 @@
 #include "wal_hash.h"
 
 namespace forst {
-
-#ifdef FORST_DIAG
-hipError_t launch_wal_verify_wave(const WalArgs& a, hipStream_t stream, const char** name);
-hipError_t launch_wal_record_crc_wave(const WalArgs& a, hipStream_t stream, const char** name);
-#endif
 
 namespace {
 
@@ -373,59 +366,13 @@ struct A14Frags {
   __device__ bool use(uint64_t q) const { return (pinfo[q] >> 20) & 1u; }
 };
 
-#ifdef FORST_DIAG
-// ---- raw CRC of a record list split by size (A/B variant) -------------------
-// WAL records span 7 B .. 32 KiB: with FORST_WAL_SPLIT=1 small ones go to the
-// rows kernel (one record per 16-lane row), large ones to the v2 kernel (one
-// per wave), results scattered back in record order.  Measured slower than
-// one rows launch over all records (C5 0.478 vs 0.499), so not the default.
-constexpr uint32_t kSplitBytes = 8192;
-
-__global__ void __launch_bounds__(kTile) split_flag_kernel(const uint32_t* len, uint64_t n,
-                                                           uint64_t* flag) {
-  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kTile + threadIdx.x;
-  if (i < n) flag[i] = len[i] < kSplitBytes ? 1 : 0;
-}
-
-__global__ void __launch_bounds__(kTile) split_compact_kernel(
-    const uint64_t* off, const uint32_t* len, uint64_t n, const uint64_t* flag,
-    const uint64_t* pos, uint64_t* s_off, uint32_t* s_len, uint64_t* b_off, uint32_t* b_len) {
-  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kTile + threadIdx.x;
-  if (i >= n) return;
-  if (flag[i]) {
-    s_off[pos[i]] = off[i];
-    s_len[pos[i]] = len[i];
-  } else {
-    b_off[i - pos[i]] = off[i];
-    b_len[i - pos[i]] = len[i];
-  }
-}
-
-__global__ void __launch_bounds__(kTile) split_scatter_kernel(uint64_t n, const uint64_t* flag,
-                                                              const uint64_t* pos,
-                                                              const uint32_t* s_out,
-                                                              const uint32_t* b_out,
-                                                              uint32_t* out) {
-  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kTile + threadIdx.x;
-  if (i < n) out[i] = flag[i] ? s_out[pos[i]] : b_out[i - pos[i]];
-}
-
-#endif  // FORST_DIAG
-
 size_t up256(size_t b) { return (b + 255) & ~size_t(255); }
-
-#ifdef FORST_DIAG
-// diagnostics build: FORST_WAL_VARIANT=wave selects the one-wave-per-log-block
-// kernels (crc32c.hip), the A/B reference of this pipeline
-bool wave_variant() { return std::string(diag_env("FORST_WAL_VARIANT")) == "wave"; }
-#endif
 
 }  // namespace
 
 namespace {
 
 // out[i] = crc32c::Extend(0, base + off[i], len[i]) for a record list
-// (FORST_WAL_SPLIT=1: split by size between the rows and v2 kernels)
 #ifndef FORST_WAL_EXPECT
 #define FORST_WAL_EXPECT 1
 #endif
@@ -440,75 +387,15 @@ hipError_t crc_records(const uint8_t* base, uint64_t base_len, const uint64_t* o
   b.out32 = out;
   b.n = n;
   b.expect = expect;  // (out pre-filled with it)
-  // default: one launch (the rows kernel for this size mix); the split is an
-  // A/B variant (C5: 0.499 one launch vs 0.478 split, tools/wal_ab.py)
-#ifndef FORST_DIAG
+  // one launch (the rows kernel for this size mix); splitting the records by
+  // size over two kernels measured slower (C5: 0.499 one launch vs 0.478)
   return launch_crc32c_blocks(kModeRaw, b, stream, name);
-#else
-  if (std::string(diag_env("FORST_WAL_SPLIT")) != "1")
-    return launch_crc32c_blocks(kModeRaw, b, stream, name);
-  const uint64_t nt = (n + kTile - 1) / kTile;
-  const dim3 grid(static_cast<uint32_t>(nt));
-  const size_t s8 = up256(8 * n), s4 = up256(4 * n), st = up256(8 * (nt + 1));
-  void* scratch = nullptr;
-  hipError_t e = scratch_alloc(&scratch, 4 * s8 + 4 * s4 + st, stream);
-  if (e != hipSuccess) return e;
-  uint8_t* p = static_cast<uint8_t*>(scratch);
-  uint64_t* flag = reinterpret_cast<uint64_t*>(p);
-  uint64_t* pos = reinterpret_cast<uint64_t*>(p + s8);
-  uint64_t* s_off = reinterpret_cast<uint64_t*>(p + 2 * s8);
-  uint64_t* b_off = reinterpret_cast<uint64_t*>(p + 3 * s8);
-  uint32_t* s_len = reinterpret_cast<uint32_t*>(p + 4 * s8);
-  uint32_t* b_len = reinterpret_cast<uint32_t*>(p + 4 * s8 + s4);
-  uint32_t* s_out = reinterpret_cast<uint32_t*>(p + 4 * s8 + 2 * s4);
-  uint32_t* b_out = reinterpret_cast<uint32_t*>(p + 4 * s8 + 3 * s4);
-  uint64_t* tiles = reinterpret_cast<uint64_t*>(p + 4 * s8 + 4 * s4);
-  hipLaunchKernelGGL(split_flag_kernel, grid, dim3(kTile), 0, stream, len, n, flag);
-  scan_u64(flag, n, tiles, pos, stream);
-  const uint64_t nst = (n + kScanTile - 1) / kScanTile;
-  uint64_t n_small = 0;
-  if ((e = hipMemcpyAsync(&n_small, tiles + nst, 8, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
-      (e = hipStreamSynchronize(stream)) != hipSuccess) {
-    (void)scratch_free(scratch, stream);
-    return e;
-  }
-  hipLaunchKernelGGL(split_compact_kernel, grid, dim3(kTile), 0, stream, off, len, n, flag, pos,
-                     s_off, s_len, b_off, b_len);
-  if (n_small) {
-    BlockArgs bs = b;
-    bs.offsets = s_off;
-    bs.sizes = s_len;
-    bs.out32 = s_out;
-    bs.n = n_small;
-    bs.kernel_hint = 1;
-    e = launch_crc32c_blocks(kModeRaw, bs, stream, name);
-  }
-  if (e == hipSuccess && n_small < n) {
-    BlockArgs bb = b;
-    bb.offsets = b_off;
-    bb.sizes = b_len;
-    bb.out32 = b_out;
-    bb.n = n - n_small;
-    bb.kernel_hint = 2;
-    e = launch_crc32c_blocks(kModeRaw, bb, stream, name);
-  }
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(split_scatter_kernel, grid, dim3(kTile), 0, stream, n, flag, pos, s_out,
-                       b_out, out);
-    e = hipGetLastError();
-  }
-  const hipError_t f = scratch_free(scratch, stream);
-  return e != hipSuccess ? e : f;
-#endif  // FORST_DIAG
 }
 
 }  // namespace
 
 hipError_t launch_wal_verify(const WalArgs& a, hipStream_t stream, const char** name) {
   if (a.n_blocks == 0) return hipSuccess;
-#ifdef FORST_DIAG
-  if (wave_variant()) return launch_wal_verify_wave(a, stream, name);
-#endif
   const uint64_t n_tiles = (a.n_blocks + kTile - 1) / kTile;
   const size_t nb = a.n_blocks;
   const size_t sz_cnt = up256(4 * nb), sz_stop = up256(4 * nb), sz_base = up256(8 * nb),
@@ -559,9 +446,6 @@ hipError_t launch_wal_verify(const WalArgs& a, hipStream_t stream, const char** 
 
 hipError_t launch_wal_record_crc(const WalArgs& a, hipStream_t stream, const char** name) {
   if (a.n_records == 0) return hipSuccess;
-#ifdef FORST_DIAG
-  if (wave_variant()) return launch_wal_record_crc_wave(a, stream, name);
-#endif
   const size_t n = a.n_records;
   // the lengths given (the writer's own, forst_wal_record_crc_lengths): the
   // rows kernel takes header offsets and payload lengths as its descriptors,

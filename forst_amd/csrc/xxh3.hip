@@ -10,9 +10,6 @@
 // non-linear scramble (xxhash.h:4962-4977) is applied in order, per
 // accumulator, by the lanes that own it.  Short inputs (<= 240 B) run the
 // reference's length-class formulas redundantly on all lanes.
-#include <cstdlib>
-#include <string>
-
 #include "crc32c_tables.h"
 #include "crc_lds.h"
 #include "device_common.h"
@@ -35,12 +32,9 @@ constexpr uint32_t kRowsThreads = kRowsWaves * 64;
 #define FORST_XX_WG_CHUNK 4
 #endif
 constexpr uint32_t kXxWgChunk = FORST_XX_WG_CHUNK;
-// block modes: results staged in LDS and stored after the loop (1) or as
-// rows finish (0); the workgroup's first kXxStageW results (96 KiB: the
-// kernel runs one 12-wave workgroup per CU for its registers anyway)
-#ifndef FORST_XX_STAGE
-#define FORST_XX_STAGE 1
-#endif
+// block modes: results staged in LDS and stored after the loop, not as rows
+// finish; the workgroup's first kXxStageW results (96 KiB: the kernel runs
+// one 12-wave workgroup per CU for its registers anyway)
 constexpr uint32_t kXxStageW = 16384;
 // bytes a block weighs in the workgroup ranges on top of its own (its
 // set-up and finish): see wg_range.  A/B on one box, 3 alternating runs
@@ -55,28 +49,16 @@ constexpr uint32_t kXxStageW = 16384;
 #define FORST_XX_BLOCK_COST 256
 #endif
 // fused WAL recovery: one CRC chain per lane through its four chunks of a
-// window (1: a 240-byte hop between chunks, J244, so a fragment's finish
-// needs no column merge), or one chain per chunk column (0: the round-3
-// form, a 1008-byte hop, J1012, and three C256 shifts in every finish)
-#ifndef FORST_FRAG_ONECHAIN
-#define FORST_FRAG_ONECHAIN 1
-#endif
-constexpr uint32_t kNC = FORST_FRAG_ONECHAIN ? 1 : 4;
-// the fragment kernel's lane constants recomputed where used (1) or left to
-// the compiler, which hoists and, at 168 VGPRs, spills them (0)
-#ifndef FORST_FRAG_FRESH
-#define FORST_FRAG_FRESH 1
-#endif
-// the fused CRC's byte masks (bytes of a 16-byte chunk inside the fragment)
-// read from a 17-entry LDS table (1), or computed in a branch per chunk (0)
-#ifndef FORST_FRAG_MASK_LDS
-#define FORST_FRAG_MASK_LDS 1
-#endif
-#if FORST_FRAG_FRESH
-#define FR(x) fresh(x)
-#else
-#define FR(x) (x)
-#endif
+// window (a 240-byte hop between chunks, J244, so a fragment's finish needs
+// no column merge; the round-3 form, one chain per chunk column, paid a
+// 1008-byte hop and three C256 shifts in every finish).  The chain state is
+// kept as kNC-element arrays: as plain scalars the compiler orders one
+// instruction of xxh3_frag_kernel<3, true, 1> differently.
+constexpr uint32_t kNC = 1;
+// The fragment kernel's lane constants are recomputed where used (fresh()):
+// left to the compiler they are hoisted and, at 168 VGPRs, spilled.
+// The fused CRC's byte masks (bytes of a 16-byte chunk inside the fragment)
+// are read from a 17-entry LDS table, not computed in a branch per chunk.
 // the fragment kernel (WAL records): 4-wave workgroups and the global feed
 // (the workgroup feed measured 5 % slower on C5's log-uniform records)
 constexpr bool kFragWg = false;
@@ -613,9 +595,7 @@ __device__ __forceinline__ void xx_step_round(const XBlk& b, uint32_t r, uint32_
   }
 }
 
-// PROBE = 1 (diagnostics build only, FORST_XXH3_VARIANT=probe_load): same
-// loads and control flow, data only XOR-folded, every block reported ok.
-template <int MODE, int PROBE>
+template <int MODE>
 __device__ __forceinline__ void xxh3_stream_body(const BlockArgs& a) {
   __shared__ uint64_t cold[4 * kColdN];
   if (threadIdx.x < 4 * kColdN) cold[threadIdx.x] = (&kXxCold[0][0])[threadIdx.x];
@@ -675,18 +655,7 @@ __device__ __forceinline__ void xxh3_stream_body(const BlockArgs& a) {
     else
       xx_issue(a.base, lane, C, r + 1, nx);
     uint64_t h = 0;
-    if (PROBE) {
-      uint32_t f = 0;
-#pragma unroll
-      for (int q = 0; q < kXxRound; ++q) f ^= cu.x[q][0] ^ cu.x[q][1] ^ cu.x[q][2] ^ cu.x[q][3] ^ cu.x[q][4];
-      acc0 ^= f ^ cu.l[0] ^ cu.l[4] ^ cu.t0;
-      if (!last) {
-        ++r;
-        return true;
-      }
-      h = __ballot(static_cast<uint32_t>(acc0) == 0x9e3779b9u) ? 1 : 0;
-      acc0 = 0;
-    } else if (!C.slow) {
+    if (!C.slow) {
       if (r == 0) {  // XXH3_INIT_ACC (xxhash.h:5188)
         acc0 = ck[kColdI0];
         acc1 = ck[kColdI1];
@@ -720,10 +689,6 @@ __device__ __forceinline__ void xxh3_stream_body(const BlockArgs& a) {
       if (MODE == kModeVerify) stored = retire(ldu32(p + C.size + 1));
     }
     if ((MODE == kModeCompute || MODE == kModeTrailer) && a.last_bytes) lastb = C.extra;
-    if (PROBE) {  // report ok: computed == stored
-      lastb = 0;
-      stored = static_cast<uint32_t>(h) + C.mod;
-    }
     uint32_t out, hi = 0, st = 0, ok = C.valid ? 1u : 0u;
     if (MODE == kModeRaw) {
       out = static_cast<uint32_t>(h);
@@ -762,14 +727,8 @@ __device__ __forceinline__ void xxh3_stream_body(const BlockArgs& a) {
 
 template <int MODE>
 __global__ void __launch_bounds__(kThreads) xxh3_stream_kernel(BlockArgs a) {
-  xxh3_stream_body<MODE, 0>(a);
+  xxh3_stream_body<MODE>(a);
 }
-
-#ifdef FORST_DIAG
-__global__ void __launch_bounds__(kThreads) xxh3_stream_probe_kernel(BlockArgs a) {
-  xxh3_stream_body<kModeVerify, 1>(a);
-}
-#endif
 
 // ---------------------------------------------------------------------------
 // XXH3 v2 ("rows"): four messages per wave, one per 16-lane row.
@@ -906,7 +865,7 @@ __global__ void __launch_bounds__(kRowsThreads) FORST_WAVES_PER_EU(3)
   // block modes: results staged in LDS and stored after the loop by the
   // whole workgroup (as crc32c_rows_kernel: stores share vmcnt with the
   // stream's loads), so every wave reaches the end: no early return
-  constexpr bool kStage = FORST_XX_STAGE && MODE != kModeRaw;
+  constexpr bool kStage = MODE != kModeRaw;
   __shared__ uint32_t st_out[kStage ? kXxStageW : 1];
   __shared__ uint8_t st_ok[kStage ? kXxStageW : 4];  // verify: ok; else: valid
   __shared__ uint8_t st_lb[MODE == kModeTrailer && kStage ? kXxStageW : 4];
@@ -1258,7 +1217,7 @@ __device__ __forceinline__ void frag_issue(const BlockArgs& a, uint32_t lane, co
       // it), its XXH3 chunk (xxh3_short_row) in x[2] and the 16 bytes after
       // that in x[3], whose first dword realigns it (the record ends >=
       // kFragTail bytes before the log end)
-      const uint64_t sp = short_phys(P0, P.size, FR(lane) & 15u);
+      const uint64_t sp = short_phys(P0, P.size, fresh(lane) & 15u);
       if (shrt) {
         pq = a.base + (sp & ~3ull) + 16 * (k - 2);
         mm = static_cast<uint32_t>(sp) & 3u;
@@ -1301,7 +1260,7 @@ __device__ __forceinline__ void frag_issue(const BlockArgs& a, uint32_t lane, co
       q0 = R + 256 * ks;
       q4 = q0 + 16;
     } else if (lastp && s4 == ql) {
-      const uint64_t lq = P0 + (P.size - 64u + 16u * (FR(lane) & 3u)) +
+      const uint64_t lq = P0 + (P.size - 64u + 16u * (fresh(lane) & 3u)) +
                             static_cast<uint64_t>(hs) * (P.info >> 8);
       q0 = a.base + (lq & ~3ull);
       q4 = (lq & 3) ? q0 + 16 : q0;  // (the stripe ends at the record end)
@@ -1328,8 +1287,8 @@ __device__ __forceinline__ void frag_issue(const BlockArgs& a, uint32_t lane, co
 // WPE: waves per SIMD the register allocation targets (3, the default: round
 // 5 builds, the a14 kernel 167 VGPRs and the fused one 164, no VGPR spills;
 // C5 a14 21.5 vs 24.8 ms at 2 in round 2)
-// the fused CRC's tables: [0, 64K) G and J244 (one chain per lane; J1012 for
-// the column chains) replicated (crc_lds.h), [64K, 124K) A16[1..15], [124K,
+// the fused CRC's tables: [0, 64K) G and J244 (one chain per lane)
+// replicated (crc_lds.h), [64K, 124K) A16[1..15], [124K,
 // 136K) C256[1..3]; constant trip counts (see fill_tables3)
 template <uint32_t NT>
 __device__ __forceinline__ void fill_frag_crc_tables(uint32_t* L) {
@@ -1341,7 +1300,7 @@ __device__ __forceinline__ void fill_frag_crc_tables(uint32_t* L) {
     const uint32_t i = tid + k * NT;
     const uint32_t e = (i >> 6) & 255, d = i & 63, t = (d >> 3) & 3;
     v1[k] = i < 16384 ? (d < 32 ? kCrcG[t * 256 + e]
-                                : (kNC == 1 ? kCrcJ244[t * 256 + e] : kCrcJ1012[t * 256 + e]))
+                                : kCrcJ244[t * 256 + e])
                       : 0u;
   }
 #pragma unroll
@@ -1644,7 +1603,7 @@ xxh3_frag_kernel(BlockArgs a) {
 #pragma unroll
   for (int d = 1; d < DEPTH; ++d) frag_issue<CRC>(a, lane, Q[d - 1], B[d]);
   uint64_t acc0 = 0, acc1 = 0;
-  uint32_t crc_s[kNC];  // (fused CRC) the lane's chain(s)
+  uint32_t crc_s[kNC];  // (fused CRC) the lane's chain
 #pragma unroll
   for (uint32_t k = 0; k < kNC; ++k) crc_s[k] = 0u;
   const fcrc::Lanes FK = fcrc::lanes(lane);
@@ -1667,7 +1626,7 @@ xxh3_frag_kernel(BlockArgs a) {
     // XXH3-blocks: nbC full ones (scrambled), then nbSC stripes of the last
     const uint32_t nbC = (C.size - 1) >> 10, nbSC = ((C.size - 1) & 1023) >> 6;
     if (C.g == 0) {  // XXH3_INIT_ACC (xxhash.h:5188)
-      const uint64_t* ci = cold + kColdN * (FR(lane) & 3u);
+      const uint64_t* ci = cold + kColdN * (fresh(lane) & 3u);
       acc0 = ci[kColdI0];
       acc1 = ci[kColdI1];
     }
@@ -1760,23 +1719,13 @@ xxh3_frag_kernel(BlockArgs a) {
         sumB1 += use ? c1 : 0ull;
       }
       if (CRC) {
-        const uint32_t kc = kNC == 1 ? 0u : k;  // the chain: the lane's one, or column k's
         const uint32_t q = 16 * t + 256 * k;
-#if FORST_FRAG_MASK_LDS
         const uint32_t n = hiA > q ? (hiA - q < 16u ? hiA - q : 16u) : 0u;
         const u32x4 m = *reinterpret_cast<const u32x4*>(kmask + 4 * n);
-        cs[kc] = fcrc::chunk_step(Lb, FK, cs[kc], static_cast<uint32_t>(d0) & m.x,
+        cs[0] = fcrc::chunk_step(Lb, FK, cs[0], static_cast<uint32_t>(d0) & m.x,
                                  static_cast<uint32_t>(d0 >> 32) & m.y,
                                  static_cast<uint32_t>(d1) & m.z,
                                  static_cast<uint32_t>(d1 >> 32) & m.w);
-#else
-        uint64_t m0 = ~0ull, m1 = ~0ull;
-        if (hiA < q + 16) fcrc::keep_mask(0, hiA > q ? hiA - q : 0u, m0, m1);
-        const uint64_t e0 = d0 & m0, e1 = d1 & m1;
-        cs[kc] = fcrc::chunk_step(Lb, FK, cs[kc], static_cast<uint32_t>(e0),
-                                  static_cast<uint32_t>(e0 >> 32), static_cast<uint32_t>(e1),
-                                  static_cast<uint32_t>(e1 >> 32));
-#endif
       }
     }
     if (CRC) {
@@ -1794,12 +1743,8 @@ xxh3_frag_kernel(BlockArgs a) {
 #pragma unroll
       for (uint32_t k = 0; k < kNC; ++k) ns[k] = carry ? cs[k] : 0u;
       if (carry && started && t == 15) ns[kNC - 1] ^= cu.ez[0];
-      auto row_value = [&](const uint32_t (&c)[kNC]) {  // chains -> the row's value at the window end
+      auto row_value = [&](const uint32_t (&c)[kNC]) {  // the lane's chain -> the row's value at the window end
         uint32_t v = c[kNC - 1];
-        if (kNC == 4)  // columns 0..2 onto column 3 (256 (3 - k) bytes on)
-          v ^= fcrc::shift_at(Lb, kFcOffC256, c[kNC == 4 ? 2 : 0]) ^
-               fcrc::shift_at(Lb, kFcOffC256 + 4096, c[kNC == 4 ? 1 : 0]) ^
-               fcrc::shift_at(Lb, kFcOffC256 + 8192, c[0]);
         v = t == 15 ? v : fcrc::shift_at(Lb, kFcOffA16 + 4096 * (14 - t), v);
         v = fcrc::row_ror_xor<1>(v);
         v = fcrc::row_ror_xor<2>(v);
@@ -1826,25 +1771,14 @@ xxh3_frag_kernel(BlockArgs a) {
             const uint32_t q = 16 * t + 256 * k;
             const uint32_t ka = B > q ? (B - q < 16u ? B - q : 16u) : 0u;
             const uint32_t kb = hiB > q ? (hiB - q < 16u ? hiB - q : 16u) : 0u;
-#if FORST_FRAG_MASK_LDS
             // bytes [ka, kb): mask(kb) & ~mask(ka)
             const u32x4 mb = *reinterpret_cast<const u32x4*>(kmask + 4 * (kb > ka ? kb : ka));
             const u32x4 ma = *reinterpret_cast<const u32x4*>(kmask + 4 * ka);
-            const uint32_t kc = kNC == 1 ? 0u : k;
-            sb[kc] = fcrc::chunk_step(
-                Lb, FK, sb[kc], __builtin_amdgcn_bitop3_b32(static_cast<uint32_t>(d0), mb.x, ma.x, 0x40),
+            sb[0] = fcrc::chunk_step(
+                Lb, FK, sb[0], __builtin_amdgcn_bitop3_b32(static_cast<uint32_t>(d0), mb.x, ma.x, 0x40),
                 __builtin_amdgcn_bitop3_b32(static_cast<uint32_t>(d0 >> 32), mb.y, ma.y, 0x40),
                 __builtin_amdgcn_bitop3_b32(static_cast<uint32_t>(d1), mb.z, ma.z, 0x40),
                 __builtin_amdgcn_bitop3_b32(static_cast<uint32_t>(d1 >> 32), mb.w, ma.w, 0x40));
-#else
-            const uint32_t kc = kNC == 1 ? 0u : k;
-            uint64_t m0, m1;
-            fcrc::keep_mask(ka, kb > ka ? kb : ka, m0, m1);
-            const uint64_t e0 = d0 & m0, e1 = d1 & m1;
-            sb[kc] = fcrc::chunk_step(Lb, FK, sb[kc], static_cast<uint32_t>(e0),
-                                     static_cast<uint32_t>(e0 >> 32), static_cast<uint32_t>(e1),
-                                     static_cast<uint32_t>(e1 >> 32));
-#endif
           }
           const bool endsB = pb && L - W0 <= G::kWin;
           const uint32_t VB = row_value(sb) ^ cu.ez[2];
@@ -1891,7 +1825,7 @@ xxh3_frag_kernel(BlockArgs a) {
         uint64_t d0, d1;
         const uint64_t le = C.off() + C.size + static_cast<uint64_t>(C.hs()) * (C.info >> 8);
         xx_words(cu.aux, static_cast<uint32_t>(le & 3), d0, d1);
-        const uint64_t* cf = cold + kColdN * (FR(lane) & 3u);
+        const uint64_t* cf = cold + kColdN * (fresh(lane) & 3u);
         const uint64_t a0 = acc0 + mul32to64(d0 ^ cf[kColdL0]) + d1;
         const uint64_t a1 = acc1 + d0 + mul32to64(d1 ^ cf[kColdL1]);
         uint64_t tm = mul128_fold64(a0 ^ cf[kColdM0], a1 ^ cf[kColdM1]);
@@ -1904,11 +1838,11 @@ xxh3_frag_kernel(BlockArgs a) {
         xx_words(cu.x[2], (fm >> 4) & 3u, d0, d1);
         const uint64_t P0 = C.off();
         const uint32_t pb = static_cast<uint32_t>(P0 - short_phys(P0, C.size, 0));
-        const uint64_t hs2 = xxh3_short_row(d0, d1, C.size, FR(lane) & 15u, pb, shsec);
+        const uint64_t hs2 = xxh3_short_row(d0, d1, C.size, fresh(lane) & 15u, pb, shsec);
         if (fin && valid && !lng) h = hs2;
       }
       // (the quad that loaded the last stripe: fm bit 18)
-      if (fin && (FR(lane) & 15u) == 4 * ((fm >> G::kQuad) & 1u) && a.out64)
+      if (fin && (fresh(lane) & 15u) == 4 * ((fm >> G::kQuad) & 1u) && a.out64)
         a.out64[C.rel] = valid ? h : 0ull;
 
     }
@@ -2076,9 +2010,6 @@ enum class XxKernel {
   kSimple,  // one wave per block: buffers shorter than 4 KiB
   kRows,    // one message per 16-lane row (xxh3_rows_kernel)
   kV1,      // one message per wave (xxh3_stream_kernel)
-#ifdef FORST_DIAG
-  kProbeLoad,
-#endif
 };
 
 hipError_t launch_kernel(void (*k)(BlockArgs), uint32_t grid, BlockArgs a, hipStream_t s,
@@ -2130,14 +2061,6 @@ hipError_t launch_xxh3_mode(XxKernel k, const BlockArgs& a, hipStream_t s, const
           1, std::min<uint64_t>(want, uint64_t(di.num_cus) * stream_occupancy<M>())));
       return launch_kernel(xxh3_stream_kernel<M>, grid, a, s);
     }
-#ifdef FORST_DIAG
-    case XxKernel::kProbeLoad: {
-      *name = "xxh3_stream_probe_kernel";
-      const uint32_t grid = static_cast<uint32_t>(std::max<uint64_t>(
-          1, std::min<uint64_t>(want, uint64_t(di.num_cus) * stream_occupancy<M>())));
-      return launch_kernel(xxh3_stream_probe_kernel, grid, a, s);
-    }
-#endif
   }
   return hipErrorInvalidValue;
 }
@@ -2179,9 +2102,6 @@ hipError_t launch_frag(const BlockArgs& a, hipStream_t stream, const char** name
 hipError_t launch_xxh3_frag(const BlockArgs& a, hipStream_t stream, const char** name) {
   if (a.n == 0) return hipSuccess;
   if (a.n >= 0xffffffffull || a.base_len < 4096 || !a.init_crcs) return hipErrorInvalidValue;
-#ifdef FORST_DIAG
-  if (std::string(diag_env("FORST_FRAG_WPE")) == "2") return launch_frag<2, false>(a, stream, name);
-#endif
 #ifndef FORST_FRAG_WPE_DEF
 #define FORST_FRAG_WPE_DEF 3
 #endif
@@ -2249,15 +2169,6 @@ hipError_t launch_xxh3_blocks(int mode, const BlockArgs& a, hipStream_t stream,
   // wal_hash.h's gathered records: rows would leave most rows idle while a
   // few walk 32 KiB records 1 KiB per step)
   if (a.kernel_hint == 3 && a.base_len >= 4096) k = XxKernel::kV1;
-#ifdef FORST_DIAG
-  if (a.base_len >= 4096) {
-    const std::string v = diag_env("FORST_XXH3_VARIANT");
-    if (v == "simple") k = XxKernel::kSimple;
-    if (v == "v1") k = XxKernel::kV1;
-    if (v == "rows" && a.n < 0xffffffffull) k = XxKernel::kRows;
-    if (v == "probe_load" && mode == kModeVerify) k = XxKernel::kProbeLoad;
-  }
-#endif
   switch (mode) {
     case kModeCompute:
       return launch_xxh3_mode<kModeCompute>(k, a, stream, name);

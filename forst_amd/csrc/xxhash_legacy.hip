@@ -263,9 +263,6 @@ constexpr uint32_t kLThreads = kLWaves * 64;
 #ifndef FORST_LANE_WG_PER_CU
 #define FORST_LANE_WG_PER_CU 1
 #endif
-#ifndef FORST_LANE_TRL_STAGE
-#define FORST_LANE_TRL_STAGE 1
-#endif
 #ifndef FORST_LANE_TRL_CAP
 #define FORST_LANE_TRL_CAP 8192
 #endif
@@ -290,9 +287,9 @@ template <int MODE, bool X64>
 __global__ void __launch_bounds__(kLThreads) xxhash_lane_kernel(BlockArgs a) {
   __shared__ __attribute__((aligned(16))) uint32_t slots[kLThreads * kLSlot / 4];
   // trailer mode: (descriptor, checksum) pairs written after the loop
-  __shared__ TrlEntry s_trl[FORST_LANE_TRL_STAGE && MODE == kModeTrailer ? kTrlCap : 1];
+  __shared__ TrlEntry s_trl[MODE == kModeTrailer ? kTrlCap : 1];
   __shared__ uint32_t s_ntrl;
-  if (FORST_LANE_TRL_STAGE && MODE == kModeTrailer) {
+  if (MODE == kModeTrailer) {
     if (threadIdx.x == 0) s_ntrl = 0;
     __syncthreads();
   }
@@ -566,7 +563,7 @@ __global__ void __launch_bounds__(kLThreads) xxhash_lane_kernel(BlockArgs a) {
         if (a.out32) a.out32[i] = c;
         if (MODE == kModeTrailer) {
           uint32_t slot = kTrlCap;
-          if (FORST_LANE_TRL_STAGE && (i >> 32) == 0) slot = atomicAdd(&s_ntrl, 1u);
+          if ((i >> 32) == 0) slot = atomicAdd(&s_ntrl, 1u);
           if (slot < kTrlCap) {
             s_trl[slot] = TrlEntry{static_cast<uint32_t>(i), c};
           } else {  // (the staging area is full: stored here)
@@ -579,7 +576,7 @@ __global__ void __launch_bounds__(kLThreads) xxhash_lane_kernel(BlockArgs a) {
       have = false;
     }
   }
-  if (FORST_LANE_TRL_STAGE && MODE == kModeTrailer) {
+  if (MODE == kModeTrailer) {
     // the staged trailers, stored once every wave of the workgroup is done
     // (stores share vmcnt with the loads: inside the loop every later step
     // waited for them); the type byte is the caller's (last_bytes) or the
@@ -594,10 +591,6 @@ __global__ void __launch_bounds__(kLThreads) xxhash_lane_kernel(BlockArgs a) {
     }
   }
 }
-
-#ifndef FORST_LEGACY_LANE
-#define FORST_LEGACY_LANE 1
-#endif
 
 template <bool X64>
 hipError_t launch_mode(int mode, const BlockArgs& a, hipStream_t stream, uint32_t grid,
@@ -678,7 +671,7 @@ hipError_t launch_xxhash_legacy_blocks(bool x64, int mode, const BlockArgs& a,
   if (a.n == 0) return hipSuccess;
   // (the lane kernel's realignment loads read the 4 bytes in front of an
   // unaligned block start: buffers shorter than 4 KiB keep the group kernel)
-  if (FORST_LEGACY_LANE && a.base_len >= 4096)
+  if (a.base_len >= 4096)
     return x64 ? launch_lane<true>(mode, a, stream, name) : launch_lane<false>(mode, a, stream, name);
   const uint64_t per_wg = uint64_t(kWaves) * kMsgsPerWave;
   const uint32_t grid = static_cast<uint32_t>(

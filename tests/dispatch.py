@@ -27,7 +27,7 @@ import numpy as np
 # ---- constants of the launch code -----------------------------------------
 CRC_WAVES = 16           # crc32c.hip: constexpr uint32_t kWaves = 16;
 XX_ROWS_WAVES = 12       # xxh3.hip: constexpr uint32_t kRowsWaves = 12;
-RAW_SPLIT = 256          # crc32c.hip: #define FORST_RAW_SPLIT 256
+RAW_SPLIT = 256          # crc32c.hip: kRawSplit
 CRC_STAGE_W = 6144       # crc32c.hip: constexpr uint32_t kStageW = 6144;
 XX_STAGE_W = 16384       # xxh3.hip: constexpr uint32_t kXxStageW = 16384;
 CRC_BLOCK_COST = 0       # crc32c.hip: #define FORST_CRC_BLOCK_COST 0
@@ -145,7 +145,7 @@ STRADDLE = np.arange(RAW_SPLIT - 32, RAW_SPLIT + 32)  # the 64 lengths around th
 def raw_crc_batch(num_cus, fill=True, seed=0xC0C):
     """A raw CRC32C batch past the small-batch dispatch AND the static shares
     of the feed: n about 20 % above 128 * 16 * num_cus.  The 64 lengths
-    straddling FORST_RAW_SPLIT each at all 16 start alignments (16 copies in a
+    straddling kRawSplit each at all 16 start alignments (16 copies in a
     row, the gap chosen so that the start moves by an odd number of bytes),
     lengths 0..16, the bulk random in 0..600, one message in a thousand
     4 KiB..70 KB, gaps 0..8, a per-message init."""

@@ -142,7 +142,7 @@ def raw_crc():
 @pytest.mark.parametrize("order", ["file", "permuted"])
 def test_raw_crc32c_lane_and_filter_kernels_with_init(raw_crc, order):
     """crc32c::Extend(init, data, n) through crc32c_raw_lane_kernel (messages
-    under FORST_RAW_SPLIT, its unstep start from the init) and
+    under kRawSplit, its unstep start from the init) and
     crc32c_rows_raw_filt_kernel (the rest, static shares then claimed chunks),
     descriptors in file order and in a random permutation"""
     r = raw_crc

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """tools/prof_a14.py -- A/B timing of the C5 a14 record XXH3 and the fused
-recovery alone (no result checks: timing-only kernel variants of the
-diagnostics builds run through it).  Prints one JSON line."""
+recovery alone, with no result checks (the library is the product's or a
+`make variant` build, tools/with_lib.py).  Prints one JSON line."""
 import json
 import os
 import sys

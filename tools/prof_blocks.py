@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """tools/prof_blocks.py <config> -- A/B timing of one block config's write side
-(trailer pass) and read side (verify pass) alone, with no result checks, so
-timing-only kernel variants of the A/B builds can run through it.  Prints one
+(trailer pass) and read side (verify pass) alone, with no result checks (the
+library is the product's or a `make variant` build).  Prints one
 JSON line: HIP-event ms per pass and the verify fraction of 8 TB/s."""
 import json
 import os
