@@ -213,7 +213,9 @@ __device__ __forceinline__ bool blk_geometry(const uint8_t* base, uint64_t o, ui
   const uint32_t nb = ldu8(base + o + s - 6) | (ldu8(base + o + s - 5) << 8);
   const uint32_t map = static_cast<uint16_t>(s - 4 - 2 - nb);
   ro = static_cast<uint32_t>(static_cast<uint64_t>(map) - static_cast<uint64_t>(nr) * 4);
-  return ro <= map;
+  // (a bucket count over the block's size wraps map, up to 64 KiB past the
+  // block: a restart array the reference would read out of bounds -- no block)
+  return ro <= map && (map <= s || nr == 0);
 }
 
 // One walk over a block's entries [0, restart offset) as the block iterators
@@ -272,20 +274,22 @@ __device__ uint32_t blk_walk(const uint8_t* base, uint64_t o, uint32_t s, uint32
     const uint64_t v0 = p + non_shared;
     if (delta_v4 && v0 > end) return kBlkBadEntry;
     if (delta_v4) {  // IndexValue::DecodeFrom: the bytes it consumes are the raw value
+      // (a varint that does not decode inside the entries fails DecodeFrom with
+      // nothing of it consumed; DecodeCurrentValue only asserts, so the value
+      // ends at the bytes consumed so far and the walk goes on from there)
       uint64_t q = v0, x;
-      uint32_t n = blk_varint64(base, q, end, x);
-      if (!n) return kBlkBadEntry;
+      uint32_t n = blk_varint64(base, q, end, x);  // handle offset, or the size delta
       q += n;
-      if (shared == 0) {  // full handle: offset, size
+      if (n && shared == 0) {  // full handle: offset, size
         n = blk_varint64(base, q, end, x);
-        if (!n) return kBlkBadEntry;
         q += n;
       }
-      if (first_key) {
+      if (n && first_key) {
         uint32_t fl;
         n = wb_varint(base, q, end, fl);
-        if (!n || end - (q + n) < fl) return kBlkBadEntry;
-        q += n + fl;
+        // (a first key running past the entries fails GetLengthPrefixedSlice
+        // with its length consumed: the value ends behind the length)
+        if (n) q += n + (end - (q + n) < fl ? 0 : fl);
       }
       vlen = static_cast<uint32_t>(q - v0);
     }

@@ -424,32 +424,54 @@ class BlockKind(enum.IntFlag):
 
 
 def block_kv_checksum_batch(base, block_offsets, block_sizes, kinds, protection_bytes,
-                            capacity=None, stream=None):
+                            capacity=None, stream=None, kv_checksums=None, prot=None,
+                            first_key=None, status=None):
     """Block::Initialize{Data,Index,MetaIndex}BlockProtectionInfo per block
     (table/block_based/block.cc:1113-1235), decoded on the device.  Returns
     (kv_checksums u8, prot u64, first_key, status): block b's kv_checksum_ is
-    kv_checksums[first_key[b] * pb : first_key[b+1] * pb].  Synchronous."""
+    kv_checksums[first_key[b] * pb : first_key[b+1] * pb].  Synchronous.
+    kv_checksums / prot / first_key / status: the caller's own output tensors
+    (u8[capacity * pb], u64[capacity], i64[n + 1], u8[n]); with kv_checksums
+    given and no capacity, the capacity is what kv_checksums (and prot) hold."""
     _dev_u8(base)
     n = _desc(block_offsets, block_sizes)
     dev = base.device
-    first = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    status = torch.empty(n, dtype=torch.uint8, device=dev)
+    first = first_key
+    if first is None:
+        first = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    assert first.is_cuda and first.dtype in (torch.int64, torch.uint64) and first.is_contiguous()
+    assert first.numel() >= n + 1
+    if status is None:
+        status = torch.empty(n, dtype=torch.uint8, device=dev)
+    assert status.is_cuda and status.dtype == torch.uint8 and status.is_contiguous()
+    assert status.numel() >= n
     total = ctypes.c_uint64()
     args = (base.data_ptr(), base.numel(), block_offsets.data_ptr(), block_sizes.data_ptr(),
             kinds.data_ptr(), n, protection_bytes, first.data_ptr())
+    if capacity is None and kv_checksums is not None:
+        capacity = kv_checksums.numel() // protection_bytes
+        if prot is not None:
+            capacity = min(capacity, prot.numel())
     if capacity is None:
         rc = lib().forst_block_kv_checksum_batch(*args, None, None, 0, None, ctypes.byref(total),
                                                  _stream(stream))
         if rc != 0 and total.value == 0:
             check(rc)
         capacity = total.value
-    enc = torch.empty(max(1, capacity) * protection_bytes, dtype=torch.uint8, device=dev)
-    prot = torch.empty(max(1, capacity), dtype=torch.uint64, device=dev)
+    enc = kv_checksums
+    if enc is None:
+        enc = torch.empty(max(1, capacity) * protection_bytes, dtype=torch.uint8, device=dev)
+    _dev_u8(enc)
+    assert enc.numel() >= capacity * protection_bytes
+    if prot is None:
+        prot = torch.empty(max(1, capacity), dtype=torch.uint64, device=dev)
+    assert prot.is_cuda and prot.dtype in (torch.int64, torch.uint64) and prot.is_contiguous()
+    assert prot.numel() >= capacity
     check(lib().forst_block_kv_checksum_batch(*args, enc.data_ptr(), prot.data_ptr(), capacity,
                                               status.data_ptr(), ctypes.byref(total),
                                               _stream(stream)))
     m = total.value
-    return enc[:m * protection_bytes], prot[:m], first, status
+    return enc[:m * protection_bytes], prot[:m], first[:n + 1], status[:n]
 
 
 def fill_stream(dev_u8, start, seed, stream=None):

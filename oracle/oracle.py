@@ -385,6 +385,222 @@ def write_batch_protect(rep):
     return (14 if len(out) != count else 0), out
 
 
+BLK_STATUS = {0: "OK", 1: "bad block contents", 2: "Corruption: bad entry in block"}
+_BLK_MAX_HASH_INDEX = 1 << 16  # kMaxBlockSizeSupportedByHashIndex (data_block_hash_index.h:71)
+
+
+class NoReferenceTwin(Exception):
+    """the reference cannot answer this block: it would not terminate, or would
+    write past its kv_checksum_ allocation"""
+
+
+def _varint64(b, p, end):
+    """GetVarint64Ptr over [p, end) (util/coding.cc): (value, next p) or None"""
+    r = 0
+    for j in range(10):
+        if p + j >= end:
+            return None
+        x = b[p + j]
+        r |= (x & 127) << (7 * j)
+        if not x & 128:
+            return r & (2**64 - 1), p + j + 1
+    return None
+
+
+class _BlockIter:
+    """BlockIter<TValue> (table/block_based/block.h, block.cc:635-774) as the
+    release build runs it: the asserts of DecodeEntry / DecodeCurrentValue are
+    no checks.  kind 0 data (DecodeEntry), 1 index (DecodeEntryV4 +
+    IndexValue::DecodeFrom, or DecodeEntry when value_is_full), 2 metaindex
+    (CheckAndDecodeEntry)."""
+
+    def __init__(self, b, restarts, num_restarts, kind):
+        self.b, self.n = b, len(b)
+        self.restarts, self.num_restarts = restarts, num_restarts
+        self.k = kind & 3
+        self.delta_v4 = self.k == 1 and not kind & 4
+        self.first_key = bool(kind & 8)
+        self.ok = True
+        self.valid = False
+        self.key, self.v0, self.vlen = b"", restarts, 0
+        self.stats = None  # counters of the final walk (block_entries(stats=))
+
+    def _count(self, what):
+        if self.stats is not None:
+            self.stats[what] = self.stats.get(what, 0) + 1
+
+    def restart_point(self, i):  # GetRestartPoint
+        return struct.unpack_from("<I", self.b, self.restarts + 4 * i)[0]
+
+    def next_entry_offset(self):
+        return self.v0 + self.vlen
+
+    def seek_to_restart_point(self, i):
+        self.key = b""
+        self.v0, self.vlen = self.restart_point(i), 0
+
+    def _corrupt(self):  # CorruptionError(): "bad entry in block"
+        self.ok = self.valid = False
+        self.key = b""
+        return False
+
+    def parse_next(self):
+        """ParseNextKey<DecodeEntryFunc> (+ IndexBlockIter::DecodeCurrentValue)"""
+        b, limit, n = self.b, self.restarts, self.n
+        p = self.next_entry_offset()
+        if p >= limit:
+            self.valid = False
+            return False
+        checked = self.k == 2
+        if (checked or self.delta_v4) and limit - p < 3:
+            return self._corrupt()
+        if p + 3 > n:
+            return self._corrupt()  # no reference twin: header bytes past the block
+        shared, non_shared = b[p], b[p + 1]
+        vlen = 0 if self.delta_v4 else b[p + 2]
+        if (shared | non_shared | vlen) < 128:
+            p += 2 if self.delta_v4 else 3
+        else:
+            self._count("entries_slow_path")
+            for which in range(2 if self.delta_v4 else 3):
+                v = _wb_varint(b, p, limit)
+                if v is None:
+                    return self._corrupt()
+                self._count("varint_%d_bytes" % (v[1] - p))
+                if which == 0:
+                    shared = v[0]
+                elif which == 1:
+                    non_shared = v[0]
+                else:
+                    vlen = v[0]
+                p = v[1]
+        if checked and limit - p < ((non_shared + vlen) & 0xFFFFFFFF):
+            return self._corrupt()
+        if p + non_shared + vlen > n:
+            return self._corrupt()  # no reference twin: key / value past the block
+        if len(self.key) < shared:
+            return self._corrupt()
+        self.key = self.key[:shared] + b[p:p + non_shared]
+        v0 = p + non_shared
+        if self.delta_v4:
+            if v0 > limit:
+                return self._corrupt()  # no reference twin: Slice of negative size
+            q = v0  # IndexValue::DecodeFrom (format.cc:123-148); a failure only asserts
+            good = True
+            for _ in range(1 if shared else 2):  # delta size | BlockHandle offset, size
+                v = _varint64(b, q, limit)
+                if v is None:
+                    good = False
+                    break
+                q = v[1]
+            if good and self.first_key:  # GetLengthPrefixedSlice: the varint stays consumed
+                v = _wb_varint(b, q, limit)
+                if v is not None:
+                    q = v[1] + (v[0] if limit - v[1] >= v[0] else 0)
+            vlen = q - v0
+        self.v0, self.vlen = v0, vlen
+        self.valid = True
+        return True
+
+
+def _block_geometry(b):
+    """Block::Block (block.cc:1058-1111, NumRestarts :1016, IndexType :1038,
+    DataBlockHashIndex::Initialize): (num_restarts, restart_offset) or None for
+    the size_ = 0 error marker"""
+    n = len(b)
+    if n < 4:
+        return None
+    footer = struct.unpack_from("<I", b, n - 4)[0]
+    nr, hash_index = footer, False
+    if n <= _BLK_MAX_HASH_INDEX:
+        hash_index = bool(footer >> 31)
+        nr = footer & 0x7FFFFFFF
+    if not hash_index:
+        ro = (n - (1 + nr) * 4) & 0xFFFFFFFF
+        return None if ro > n - 4 else (nr, ro)
+    if n < 6:
+        return None
+    size = (n - 4) & 0xFFFF
+    num_buckets = struct.unpack_from("<H", b, size - 2)[0]
+    map_offset = (size - 2 - num_buckets) & 0xFFFF
+    ro = (map_offset - nr * 4) & 0xFFFFFFFF
+    if ro > map_offset:
+        return None
+    if map_offset > n and nr:
+        return None  # no reference twin: the restart array lies past the block
+    return nr, ro
+
+
+def block_entries(block_bytes, kind, stats=None):
+    """-> (status, [(key bytes, value offset, value length)]) of
+    Block::Initialize{Data,Index,MetaIndex}BlockProtectionInfo's walk
+    (block.cc:1113-1235): GetRestartInterval and NumberOfKeys (block.h:484-512)
+    first, as they can fail the block, then SeekToFirst / Next.  stats (a
+    dict) counts the slow-path entries and varint widths of that last walk."""
+    b = bytes(block_bytes)
+    g = _block_geometry(b)
+    if g is None:
+        return 1, []
+    nr, ro = g
+    if nr == 0:
+        return 0, []
+    it = _BlockIter(b, ro, nr, kind)
+    if it.k == 2:  # MetaBlockIter: interval 1, num_restarts_ keys (block.h:828-829)
+        num_keys = nr
+    else:
+        interval = 0
+        if nr > 1:  # GetRestartInterval
+            it.seek_to_restart_point(0)
+            it.parse_next()
+            end_index, interval = it.restart_point(1), 1
+            while it.next_entry_offset() < end_index and it.ok:
+                if not it.parse_next() and it.ok:
+                    raise NoReferenceTwin("GetRestartInterval does not terminate")
+                interval += 1
+        num_keys = (nr - 1) * interval  # NumberOfKeys
+        if it.ok:
+            it.seek_to_restart_point(nr - 1)
+            while it.next_entry_offset() < ro and it.ok:
+                it.parse_next()
+                num_keys += 1
+    out = []
+    if it.ok:
+        it.stats = stats
+        it.seek_to_restart_point(0)
+        it.parse_next()
+        while it.valid:
+            out.append((it.key, it.v0, it.vlen))
+            it.parse_next()
+        if it.ok and len(out) > (num_keys & 0xFFFFFFFF):
+            raise NoReferenceTwin("more entries than kv_checksum_ was sized for")
+    if not it.ok:
+        return 2, []
+    return 0, out
+
+
+def block_kv_checksums(block_bytes, kind, prot_bytes):
+    """Block::Initialize{Data,Index,MetaIndex}BlockProtectionInfo restated
+    (table/block_based/block.cc:1113-1235 over Block::Block :1058-1111 and the
+    block iterators' entry decoding): (status -- 0 OK, 1 bad block contents,
+    2 bad entry, as include/forst_checksum.h --, key count, kv_checksum_ bytes,
+    the full 64-bit protection values).  kind: 0 data, 1 index, 2 metaindex,
+    | 4 value_is_full, | 8 index_has_first_key."""
+    b = bytes(block_bytes)
+    st, ents = block_entries(b, kind)
+    if not ents:
+        return st, 0, b"", np.zeros(0, np.uint64)
+    keys = b"".join(k for k, _, _ in ents)
+    kl = np.array([len(k) for k, _, _ in ents], np.uint32)
+    ko = np.zeros(len(ents), np.uint64)
+    ko[1:] = np.cumsum(kl[:-1].astype(np.uint64))
+    vo = np.array([v for _, v, _ in ents], np.uint64) + np.uint64(len(keys))
+    vl = np.array([n for _, _, n in ents], np.uint32)
+    base = np.frombuffer(keys + b + bytes(8), np.uint8)
+    prot = kv_protect_batch(base, ko, kl, vo, vl)  # ProtectKV(key, value)
+    enc = prot.view(np.uint8).reshape(-1, 8)[:, :prot_bytes].tobytes()  # Encode(len): LE low bytes
+    return st, len(ents), enc, prot
+
+
 def splitmix64(x):
     return lib().oracle_splitmix64(x)
 

@@ -28,6 +28,19 @@ in for) and driven through ctypes:
 Committed: tests/golden/kv_sites.npz (arrays only: numpy.load with
 allow_pickle=False) + kv_sites.json (case lists, Status texts).
 
+  --kv-blocks  writes only tests/golden/kv_blocks.{npz,json} (kv_sites.* are
+             left alone): crafted blocks from tests/blockgen.py -- block_cases():
+             2- and 3-byte varints in every header field, keys and values over
+             the hash's length classes, hash-index geometry, blocks of 64 KiB
+             and 64 KiB + 1, first keys, damage the reference reads inside the
+             block -- answered by Block::Initialize*BlockProtectionInfo for
+             protection bytes 1, 2, 4 and 8, and a few WriteBatch reps with
+             3-byte lengths and 3..5-byte column family varints.  A case the
+             reference could only answer by reading out of bounds, by writing
+             past its kv_checksum_, or not at all (its GetRestartInterval loops
+             on a bad restart array) is not recorded: oracle.block_kv_checksums
+             raises NoReferenceTwin on those, try a new case there first.
+
 Re-run:  python tests/golden/gen_kv_golden.py   (needs /root/reference + g++)
 """
 import ctypes
@@ -260,11 +273,215 @@ def gen_blocks(L, arrays, meta):
     meta["blocks"] = cases
 
 
+def block_cases():
+    """[(name, kind, block bytes)] of kv_blocks: the entry shapes, geometries
+    and in-bounds damage the SST-cut blocks of kv_sites never reach"""
+    import blockgen as G
+    P = G.pattern
+    D, I, M, F, K = G.DATA, G.INDEX, G.META, G.FULL, G.FIRST
+    out = []
+
+    # shared / non_shared / value_length at the varint32 width edges, alone and together
+    for x in (127, 128, 16383, 16384):
+        k0 = P(x, 1)
+        for name, kind in (("data", D), ("index_full", I | F), ("meta", M)):
+            long = k0[:5] + b"yy" + P(x - 7, 3)
+            ents = [(k0, b"v0"),                   # non_shared = x
+                    (k0 + b"z", b"v1"),            # shared = x
+                    (k0[:5] + b"yy", P(x, 2)),     # value_length = x
+                    (long, b""),
+                    (long + P(x, 4), P(x, 5)),     # all three = x
+                    (long + b"\xfe\xff", b"")]
+            out.append((f"varint_{name}_{x}", kind, G.build(ents, kind=kind, share_over_restarts=True)))
+        for name, kind in (("index_v4", I), ("index_v4_first", I | K)):
+            fk = (lambda j: P(j, 7)) if kind & K else (lambda j: None)
+            ents = [(k0, ((1000, 50), fk(9))), (k0 + b"z", ((1055, 60), fk(0))),
+                    (k0 + P(x, 8), ((1120, 40), fk(130))),  # shared = non_shared = x
+                    (k0 + b"zz", ((1165, 300000), fk(3)))]
+            out.append((f"varint_{name}_{x}", kind, G.build(ents, kind=kind)))
+
+    # key lengths over the hash's length classes, rebuilt from shared prefixes of
+    # every length mod 4
+    for n in (16, 17, 128, 129, 240, 241, 1024, 1025, 3001):
+        key = P(n, n)
+        ents = [(key, b"first")]
+        for r in range(4):
+            for p in (max(p for p in range(n) if p % 4 == r), 4 + r):
+                key = key[:p] + P(n - p, n + 10 * r + p)
+                if G.common_prefix(ents[-1][0], key) != p:  # the new tail must differ at once
+                    key = key[:p] + bytes([key[p] ^ 0x55]) + key[p + 1:]
+                ents.append((key, P(r + 1, p)))
+        out.append((f"keys_{n}", D, G.build(ents, kind=D, interval=16)))
+    ents = [(P(n, 40 + n), ((n * 77, n + 1), None)) for n in (16, 17, 128, 129, 240, 241, 1025)]
+    ents = [(ents[0][0][:11] + k, v) for k, v in ents]
+    out.append(("keys_index_v4", I, G.build(ents, kind=I, interval=4)))
+
+    # value lengths over the hash's length classes; restart intervals 1 and 16
+    vals = (0, 1, 3, 4, 8, 9, 16, 17, 128, 129, 240, 241, 5003)
+    for interval in (1, 16):
+        ents = [(b"user-key-%04d" % v + b"\x01" * 8, P(v, v)) for v in vals]
+        out.append((f"values_interval_{interval}", D, G.build(ents, kind=D, interval=interval)))
+        out.append((f"values_index_full_interval_{interval}", I | F,
+                    G.build(ents, kind=I | F, interval=interval)))
+    out.append(("values_meta", M, G.build(ents, kind=M)))
+
+    # data-block hash index: 1 bucket, many, a block of exactly 64 KiB; 64 KiB + 1
+    small = [(b"hk%03d" % j + P(j % 9, j), P(j % 40, j + 1)) for j in range(40)]
+    out.append(("hash_1_bucket", D, G.build(small[:3], kind=D, interval=16, hash_buckets=1)))
+    out.append(("hash_many_buckets", D, G.build(small, kind=D, interval=16,
+                                                hash_buckets=bytes(range(53)) * 5)))
+    out.append(("hash_exactly_65536", D, G.sized(65536, small, b"zfill", kind=D, interval=16,
+                                                 hash_buckets=bytes(range(37)))))
+    out.append(("plain_65537", D, G.sized(65537, small, b"zfill", kind=D, interval=16)))
+    # over 64 KiB the footer is the restart count as it stands: bit 31 is part
+    # of the count, the 6 bytes before it are entry and restart bytes, not a
+    # hash index, and the metaindex walk meets 2 stray bytes -> the error marker
+    blk = G.sized(65537, [], b"only", kind=M, hash_buckets=0)
+    assert struct.unpack_from("<I", blk, len(blk) - 4)[0] == 0x80000001
+    out.append(("bit31_65537", M, blk))
+
+    # format_version >= 4 index blocks with first keys: shared == 0 and > 0,
+    # handles of 1..5 varint64 bytes, first keys of 0 and 200 bytes
+    ents, off = [], 0
+    for j, size in enumerate((1, 100, 127, 128, 16383, 16384, (1 << 21) - 1, 1 << 21,
+                              (1 << 28) - 1, 1 << 28, (1 << 35) - 1, 77, 5, 1 << 30, 9, 3)):
+        ents.append((b"index-key-" + P(4 + j % 3, j), ((off, size), P(200 if j % 3 == 1 else 0 if j % 3 else 24, j))))
+        off += size + 5
+    for interval in (1, 4, 16):
+        out.append((f"index_v4_first_interval_{interval}", I | K, G.build(ents, kind=I | K, interval=interval)))
+    out.append(("index_v4_interval_4", I, G.build([(k, (h, None)) for k, (h, _f) in ents], kind=I, interval=4)))
+
+    # damage the reference still reads inside the block: checked decoders
+    # (metaindex, format_version >= 4 index) and the unchecked one (data)
+    def craft(entries_bytes, restarts=(0,), **kw):
+        return bytes(entries_bytes) + G.tail(list(restarts), **kw)
+
+    e_data = b"\x00\x04\x02" + b"abcd" + b"xy"          # abcd -> xy
+    e_v4 = b"\x00\x04" + b"abcd" + b"\x10\x20"          # abcd -> handle (16, 32)
+    e_v4f = e_v4 + b"\x03fk0"
+    for name, kind, good in (("data", D, e_data), ("meta", M, e_data), ("index_full", I | F, e_data),
+                             ("index_v4", I, e_v4), ("index_v4_first", I | K, e_v4f)):
+        # (metaindex: every entry a restart point)
+        r2 = (0, len(good)) if kind == M else (0,)
+        out.append((f"bad_varint_cut_at_restarts_{name}", kind, craft(good + b"\x85\x80\x80", r2)))
+        out.append((f"bad_varint_5_continuation_{name}", kind,
+                    craft(good + b"\x80\x80\x80\x80\x80\x01\x01\x01kv", r2)))
+        out.append((f"bad_shared_over_previous_{name}", kind,
+                    craft(good + b"\x05\x01" + (b"" if good is not e_data else b"\x01") + b"k" +
+                          (b"v" if good is e_data else b"\x01" + (b"\x00" if kind & K else b"")), r2)))
+        out.append((f"ok_shared_equals_previous_{name}", kind,
+                    craft(good + b"\x04\x01" + (b"" if good is not e_data else b"\x01") + b"k" +
+                          (b"v" if good is e_data else b"\x01" + (b"\x00" if kind & K else b"")), r2)))
+    # non_shared + value_length past the restart offset: the checked decoder
+    # fails, the unchecked one takes restart / hash-index bytes as value bytes
+    for name, kind in (("meta", M), ("data", D), ("index_full", I | F)):
+        r2 = (0, len(e_data)) if kind == M else (0,)
+        out.append((f"past_limit_1_byte_{name}", kind, craft(e_data + b"\x00\x01\x06" + b"k" + b"v", r2)))
+        out.append((f"past_limit_2_byte_{name}", kind,
+                    craft(e_data + b"\x00\x01\x96\x01" + b"k" + b"v" * 20, r2,
+                          hash_buckets=None if kind == M else 200)))
+    out.append(("past_limit_2_byte_data_plain", D, craft(e_data + b"\x00\x81\x00\x05" + b"k" + b"v", (0,))))
+    # an index value that does not decode inside the entries: IndexValue::DecodeFrom
+    # fails (only asserted), the value is what it consumed and the walk goes on there
+    out.append(("bad_v4_handle_size_cut", I, craft(e_v4 + b"\x00\x01k" + b"\x07\x80\x80\x80")))
+    out.append(("bad_v4_delta_cut", I, craft(e_v4 + b"\x01\x01k" + b"\x80\x80\x80")))
+    out.append(("bad_v4_handle_10_continuation", I, craft(e_v4 + b"\x00\x01k" + b"\x80" * 10 + b"\x01\x01" + e_v4)))
+    out.append(("bad_v4_first_key_varint_cut", I | K, craft(e_v4f + b"\x00\x01k\x07\x08" + b"\x80\x80\x80")))
+    out.append(("bad_v4_first_key_length_past_restarts", I | K,
+                craft(e_v4f + b"\x00\x01k\x07\x08" + b"\x32" + b"\x7f\x01k\x01\x01\x00")))
+    out.append(("v4_first_key_length_past_restarts_walk_goes_on", I | K,
+                craft(e_v4f + b"\x00\x01k\x07\x08" + b"\x32" + b"\x00\x01m\x05\x06\x00")))
+    # a hash index whose bucket count exceeds the block: the 16-bit map offset
+    # wraps to 5 bytes before the block's end, the restart array ends there and
+    # its third entry takes in the count's low byte (so it points far outside
+    # and that interval is empty): 2 intervals of 2 entries
+    four = (b"\x00\x02\x01aa1" + b"\x01\x01\x01b2", b"\x00\x02\x01cc3" + b"\x01\x01\x01d4")
+    blk = four[0] + four[1] + struct.pack("<II", 0, len(four[0])) + b"\x00\x00\x00" + b"\xff\xff" + \
+        struct.pack("<I", (1 << 31) | 3)
+    out.append(("hash_bucket_count_wraps_map_offset", D, blk))
+    # a hash-index footer with no restarts: entry bytes, but no protection
+    for name, kind in (("data", D), ("meta", M)):
+        out.append((f"hash_no_restarts_{name}", kind, e_data + G.tail([], hash_buckets=3)))
+    # an index value cut off exactly at the restart offset, nothing behind it:
+    # the value is what DecodeFrom consumed and the walk ends there, 2 keys
+    for name, kind, good in (("", I, e_v4), ("_first", I | K, e_v4f)):
+        out.append((f"v4{name}_handle_offset_cut_nothing_after", kind, craft(good + b"\x00\x01k")))
+        out.append((f"v4{name}_handle_size_cut_nothing_after", kind, craft(good + b"\x00\x01k\x07")))
+        out.append((f"v4{name}_delta_cut_nothing_after", kind, craft(good + b"\x01\x01k")))
+    out.append(("v4_first_key_varint_cut_nothing_after", I | K, craft(e_v4f + b"\x00\x01k\x07\x08")))
+    out.append(("v4_first_delta_first_key_varint_cut_nothing_after", I | K, craft(e_v4f + b"\x01\x01k\x03")))
+    return out
+
+
+def wb_extra_reps():
+    """[(name, rep)]: WriteBatch reps with 3-byte lengths and 3..5-byte column
+    family varints, which neither the reference's random batches of kv_sites nor
+    the tests' own generator produce"""
+    import blockgen as G
+    head = struct.pack("<QI", 99, 1)
+    out = [("value_20000", head + b"\x01" + b"\x03key" + G.varint(20000) + G.pattern(20000, 11))]
+    for cf in (1 << 14, 1 << 21, 1 << 28, (1 << 32) - 1):
+        out.append((f"cf_{cf}", head + b"\x05" + G.varint(cf) + b"\x03key" + b"\x05value"))
+    out.append(("cf_5_continuation", head + b"\x05" + b"\x80\x80\x80\x80\x80\x01" + b"\x03key\x05value"))
+    out.append(("two_records_big_cf", struct.pack("<QI", 7, 2) + b"\x04" + G.varint(1 << 21) + b"\x03key" +
+                b"\x06" + G.varint((1 << 32) - 1) + b"\x02ab" + G.varint(16384) + G.pattern(16384, 3)))
+    return out
+
+
+def gen_kv_blocks(L):
+    """tests/golden/kv_blocks.{json,npz}: block_cases() and wb_extra_reps(), each
+    answered by the reference (protection bytes 1, 2, 4 and 8 for the blocks)"""
+    arrays, meta = {}, {"generator": "tests/golden/gen_kv_golden.py --kv-blocks"}
+    cases, blobs = [], []
+    for name, kind, blk in block_cases():
+        buf = np.frombuffer(blk + bytes(64), np.uint8).copy()
+        c = {"name": name, "kind": kind, "size": len(blk)}
+        for pb in (1, 2, 4, 8):
+            out = np.zeros(1 << 16, np.uint8)
+            nk = L.ref_block_kv_checksum(ptr(buf), len(blk), kind & 3, pb, 1 if kind & 4 else 0,
+                                         1 if kind & 8 else 0, ptr(out), out.nbytes)
+            c[f"keys_{pb}"] = int(nk)
+            c[f"kv_checksum_{pb}"] = out[:max(0, nk) * pb].tobytes().hex()
+        if os.environ.get("GEN_DEBUG"):
+            print(name, kind, len(blk), c["keys_8"], flush=True)
+        cases.append(c)
+        blobs.append(blk)
+    pos, parts = 0, []
+    for j, b in enumerate(blobs):
+        pos += (j % 16 - pos) % 16  # block starts at every offset mod 16
+        parts.append(pos)
+        pos += len(b)
+    base = np.zeros(pos + 64, np.uint8)
+    for o, b in zip(parts, blobs):
+        base[o:o + len(b)] = np.frombuffer(b, np.uint8)
+    arrays["blk_base"] = base
+    arrays["blk_offs"] = np.array(parts, np.uint64)
+    meta["blocks"] = cases
+    reps, batches = [], []
+    for name, rep in wb_extra_reps():
+        st, prot = wb_protect(L, rep)
+        batches.append({"name": name, "status": st, "n_prot": len(prot), "len": len(rep)})
+        arrays[f"wb_prot_{len(reps)}"] = prot
+        reps.append(rep)
+    meta["writebatch"] = batches
+    arrays["wb_base"] = np.frombuffer(b"".join(reps) + bytes(64), np.uint8).copy()
+    arrays["wb_offs"] = np.cumsum([0] + [len(r) for r in reps[:-1]]).astype(np.uint64)
+    arrays["wb_lens"] = np.array([len(r) for r in reps], np.uint32)
+    npz, js = os.path.join(HERE, "kv_blocks.npz"), os.path.join(HERE, "kv_blocks.json")
+    np.savez_compressed(npz, **arrays)
+    with open(js, "w") as f:
+        json.dump(meta, f, indent=1)
+    print(npz, os.path.getsize(npz), js)
+
+
 def main():
     with tempfile.TemporaryDirectory() as td:
         so = refbuild.link_veneer([os.path.join(HERE, "ref_kv_shim.cc")],
                                   os.path.join(td, "libref_kv.so"))
         L = load(so)
+        if "--kv-blocks" in sys.argv[1:]:  # the new files only: kv_sites.* stay as they are
+            gen_kv_blocks(L)
+            return
         arrays, meta = {}, {"generator": "tests/golden/gen_kv_golden.py"}
         gen_memtable(L, arrays, meta)
         gen_writebatch(L, arrays, meta)

@@ -2,6 +2,10 @@
 tests/golden/kv_sites.{json,npz} (reference-made, gen_kv_golden.py) laid out
 as the engine's batch calls take them: memtable entry buffers with their
 corrupted copies, and the WriteBatch reps back to back."""
+import functools
+import json
+import os
+
 import numpy as np
 
 
@@ -55,6 +59,65 @@ def mem_checksum_pos(base, off):
     ikl, kp = _varint(base, off)
     vl, vp = _varint(base, kp + ikl)
     return vp + vl
+
+
+@functools.lru_cache(maxsize=None)
+def kv_blocks():
+    """tests/golden/kv_blocks.{json,npz} (gen_kv_golden.py --kv-blocks): crafted
+    blocks and WriteBatch reps answered by the reference -> (meta, arrays), in
+    the layout of kv_sites (block_case / write_batch_case take both)"""
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    with open(os.path.join(golden, "kv_blocks.json")) as f:
+        meta = json.load(f)
+    z = np.load(os.path.join(golden, "kv_blocks.npz"), allow_pickle=False)
+    return meta, {k: z[k] for k in z.files}
+
+
+def check_block_results(cases, pb, enc, prot, first, st):
+    """one batch call's outputs against the reference's answers of `cases`
+    (block b = case b): the error marker or the key count, every kv_checksum_
+    byte, and prot's low bytes = the encoded bytes"""
+    assert int(first[0]) == 0
+    for j, c in enumerate(cases):
+        name = c.get("name") or (c["src"], c["kind_name"])
+        nk = int(first[j + 1]) - int(first[j])
+        want = c[f"keys_{pb}"]
+        if want < 0:
+            assert st[j] in (1, 2) and nk == 0, (name, pb, int(st[j]), nk)
+            continue
+        assert st[j] == 0 and nk == want, (name, pb, int(st[j]), nk, want)
+        got = enc[int(first[j]) * pb:int(first[j + 1]) * pb].tobytes()
+        assert got.hex() == c[f"kv_checksum_{pb}"], (name, pb)
+        if prot is not None:
+            low = prot[int(first[j]):int(first[j + 1])].astype(np.uint64).view(np.uint8)
+            assert low.reshape(-1, 8)[:, :pb].tobytes() == got, (name, pb)
+    assert int(first[len(cases)]) * pb == len(enc)
+
+
+_restated = {}
+
+
+def restated_batch(blocks, pb):
+    """the restatement's answer for one batch call over blockgen.batch()'s
+    blocks -> (first_key i64[n + 1], status u8[n], kv_checksums u8, prot u64);
+    a None block (descriptor past the buffer) is status 3 without keys"""
+    from oracle import oracle as O
+
+    first, status, encs, prots = [0], [], [], []
+    for b in blocks:
+        if b is None:
+            st, nk, enc, prot = 3, 0, b"", np.zeros(0, np.uint64)
+        else:
+            key = (b[0], b[1], pb)
+            if key not in _restated:
+                _restated[key] = O.block_kv_checksums(b[0], b[1], pb)
+            st, nk, enc, prot = _restated[key]
+        first.append(first[-1] + nk)
+        status.append(st)
+        encs.append(enc)
+        prots.append(prot)
+    return (np.array(first, np.int64), np.array(status, np.uint8),
+            np.frombuffer(b"".join(encs), np.uint8), np.concatenate(prots + [np.zeros(0, np.uint64)]))
 
 
 def block_case(meta, arrays):

@@ -599,6 +599,54 @@ def test_emu_block_kv_checksums_vs_reference(kv_sites):
             assert got == c[f"kv_checksum_{pb}"], (c["src"], c["kind_name"])
 
 
+@pytest.mark.parametrize("pb", [1, 2, 4, 8])
+def test_emu_block_kv_checksums_crafted_vs_reference(pb):
+    """the crafted blocks of kv_blocks (gen_kv_golden.py --kv-blocks: multi-byte
+    varints in shared / non_shared / value_length, hash-index geometry, 64 KiB
+    and 64 KiB + 1 blocks, first keys, damage the reference reads in bounds)
+    in one batch call: the reference's key count or error marker, every
+    kv_checksum_ byte, and the restatement's status"""
+    import kvsites
+
+    base, offs, sizes, kinds, cases = kvsites.block_case(*kvsites.kv_blocks())
+    enc, prot, first, st = emu.block_kv_checksum(base, offs, sizes, kinds, pb)
+    kvsites.check_block_results(cases, pb, enc, prot, first, st)
+    for j, c in enumerate(cases):
+        blk = base[int(offs[j]):int(offs[j]) + int(sizes[j])].tobytes()
+        assert st[j] == O.block_kv_checksums(blk, int(kinds[j]), pb)[0], c["name"]
+
+
+def test_emu_block_kv_checksums_random_batch_vs_restatement():
+    """blockgen batches (well-formed blocks of every kind and flag, blocks
+    without restarts, damaged and tiny blocks, descriptors past the buffer, the
+    last block ending at base_len) against the oracle's restatement:
+    first_key, status, every byte and protection value"""
+    import blockgen
+    import kvsites
+
+    for seed, n, pb in ((1, 300, 8), (2, 257, 1)):
+        base, offs, sizes, kinds, blocks = blockgen.batch(np.random.default_rng(seed), n)
+        wfirst, wst, wenc, wprot = kvsites.restated_batch(blocks, pb)
+        assert wfirst[-1] > n and (wst == 3).any() and (wst == 2).any() and (wst == 1).any()
+        enc, prot, first, st = emu.block_kv_checksum(base, offs, sizes, kinds, pb)
+        assert (st == wst).all(), np.nonzero(st != wst)[0][:8]
+        assert (first.astype(np.int64) == wfirst).all()
+        assert (enc == wenc).all() and (prot == wprot).all()
+
+
+def test_emu_write_batch_long_varints_vs_reference():
+    """WriteBatch reps with a 3-byte length and 3..5-byte column family varints
+    (kv_blocks), answered by the reference"""
+    import kvsites
+
+    base, offs, lens, reps = kvsites.write_batch_case(*kvsites.kv_blocks())
+    prot, first, st, nprot = emu.write_batch_protect(base, offs, lens)
+    for j, (name, status, want) in enumerate(reps):
+        assert O.WB_STATUS[int(st[j])] == status, name
+        got = prot[int(first[j]):int(first[j]) + int(nprot[j])]
+        assert [int(x) for x in got] == [int(x) for x in want], name
+
+
 @pytest.mark.parametrize("recyclable", [False, True])
 def test_emu_wal_record_xxh3_unpacked_form(recyclable):
     """a14's unpacked bookkeeping (wal_hash.h: the flag kernel, a second scan

@@ -18,6 +18,7 @@ if not torch.cuda.is_available():
 
 from forst_amd import engine  # noqa: E402
 from oracle import oracle as O  # noqa: E402
+import blockgen  # noqa: E402
 import kvsites  # noqa: E402
 
 DEV = "cuda"
@@ -246,3 +247,188 @@ def test_block_kv_checksums_many_blocks(kv_sites):
     for q, (o, j) in enumerate(parts):
         got = enc[int(first[q]) * 8:int(first[q + 1]) * 8].tobytes().hex()
         assert got == cases[j]["kv_checksum_8"], (q, j)
+
+
+# ---- the block walk on the entry shapes the SST-cut fixtures never reach ------
+# Every output handed to the engine is prefilled with a sentinel (0xA5 bytes,
+# 0x5A5A... words) and is longer than asked for: what the kernels do not store
+# fails its comparison, what they store past the capacity fails the guard check.
+S8, S64, GUARD = 0xA5, 0x5A5A5A5A5A5A5A5A, 8
+
+
+def du(a):
+    a = np.ascontiguousarray(a)
+    signed = {np.dtype(np.uint64): np.int64, np.dtype(np.uint32): np.int32}.get(a.dtype)
+    return torch.from_numpy(a.view(signed) if signed else a).to(DEV)
+
+
+def run_blocks(base_t, offs, sizes, kinds, pb, capacity):
+    """one batch call into sentinel-filled outputs -> host (kv_checksums,
+    prot u64, first_key i64[n + 1], status); the guard cells checked"""
+    n = len(offs)
+    enc = torch.full((capacity * pb + GUARD,), S8, dtype=torch.uint8, device=DEV)
+    prot = torch.full((capacity + GUARD,), S64, dtype=torch.int64, device=DEV)
+    first = torch.full((n + 1 + GUARD,), S64, dtype=torch.int64, device=DEV)
+    status = torch.full((n + GUARD,), S8, dtype=torch.uint8, device=DEV)
+    outs = (enc, prot, first, status)
+    try:
+        e, p, f, s = engine.block_kv_checksum_batch(
+            base_t, du(offs), du(sizes), du(kinds), pb, capacity=capacity, kv_checksums=enc,
+            prot=prot, first_key=first, status=status)
+    except Exception as ex:
+        ex.outputs = tuple(host(t) for t in outs)
+        raise
+    assert (host(enc)[capacity * pb:] == S8).all() and (host(prot)[capacity:] == S64).all()
+    assert (host(first)[n + 1:] == S64).all() and (host(status)[n:] == S8).all()
+    assert len(f) == n + 1 and len(s) == n
+    return host(e), host(p).view(np.uint64), host(f), host(s)
+
+
+def same(got, want, what):
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    bad = np.nonzero(got != want)[0]
+    assert bad.size == 0, (what, int(bad.size), bad[:8].tolist(), got[bad[:8]].tolist(),
+                           want[bad[:8]].tolist())
+
+
+def check_restated(got, blocks, pb, what):
+    enc, prot, first, st = got
+    wfirst, wst, wenc, wprot = kvsites.restated_batch(blocks, pb)
+    same(st, wst, (what, "status"))
+    same(first, wfirst, (what, "first_key"))
+    same(enc, wenc, (what, "kv_checksums"))
+    same(prot, wprot, (what, "prot"))
+
+
+def _fixture_total(cases, pb):
+    return sum(max(0, c[f"keys_{pb}"]) for c in cases)
+
+
+@pytest.mark.parametrize("pb", [1, 2, 4, 8])
+def test_block_kv_checksums_crafted_fixtures(pb):
+    """the crafted blocks of kv_blocks (gen_kv_golden.py --kv-blocks), answered
+    by the reference: multi-byte varints in shared / non_shared / value_length
+    for every block kind, keys and values over every hash length class rebuilt
+    from prefixes of every length mod 4, hash-index geometry, blocks of 64 KiB
+    and 64 KiB + 1, first keys, damage the reference reads in bounds"""
+    base, offs, sizes, kinds, cases = kvsites.block_case(*kvsites.kv_blocks())
+    enc, prot, first, st = run_blocks(d(base), offs, sizes, kinds, pb, _fixture_total(cases, pb))
+    kvsites.check_block_results(cases, pb, enc, prot, first, st)
+    for j, c in enumerate(cases):  # bad contents vs bad entry: as the restatement tells them apart
+        blk = base[int(offs[j]):int(offs[j]) + int(sizes[j])].tobytes()
+        assert st[j] == O.block_kv_checksums(blk, int(kinds[j]), pb)[0], c["name"]
+
+
+@pytest.mark.parametrize("pb", [1, 2, 4, 8])
+@pytest.mark.parametrize("shift", [4, 8, 12])
+def test_block_kv_checksums_shifted_base(shift, pb):
+    """the same batch with base 4, 8 and 12 bytes past 16-byte alignment, every
+    protection width at each"""
+    base, offs, sizes, kinds, cases = kvsites.block_case(*kvsites.kv_blocks())
+    buf = torch.zeros(len(base) + 64, dtype=torch.uint8, device=DEV)
+    at = (-buf.data_ptr()) % 16 + shift
+    view = buf[at:at + len(base)]
+    view.copy_(d(base))
+    assert view.data_ptr() % 16 == shift and view.is_contiguous()
+    enc, prot, first, st = run_blocks(view, offs, sizes, kinds, pb, _fixture_total(cases, pb))
+    kvsites.check_block_results(cases, pb, enc, prot, first, st)
+
+
+_batch = {}
+
+
+def random_batch():
+    if not _batch:
+        _batch["b"] = blockgen.batch(np.random.default_rng(0xB10C), 3 * 2048 + 5)
+    return _batch["b"]
+
+
+@pytest.mark.parametrize("n,pb", [(3 * 2048 + 5, 8), (2046, 1), (2047, 2), (2048, 4), (2049, 8)])
+def test_block_kv_checksums_random_batch_vs_restatement(n, pb):
+    """n blockgen blocks (1-8 entries mostly, a tail of larger ones; every kind
+    and flag; starts at every offset mod 16, descriptors permuted; blocks
+    without restarts, damaged blocks, blocks of 0..7 bytes and descriptors past
+    base_len in between) against the oracle's restatement: all n + 1 first_key
+    values -- a scan over 2048-value tiles, n + 1 on both sides of the tile
+    edge --, every status, checksum byte and protection value"""
+    base, offs, sizes, kinds, blocks = random_batch()
+    offs, sizes, kinds, blocks = offs[:n], sizes[:n], kinds[:n], blocks[:n]
+    want = kvsites.restated_batch(blocks, pb)
+    assert {0, 1, 2, 3} <= set(want[1].tolist()) and set(kinds.tolist()) >= {0, 1, 2, 5, 9, 13}
+    assert len({int(o) % 16 for o in offs}) == 16
+    got = run_blocks(d(base), offs, sizes, kinds, pb, int(want[0][-1]))
+    check_restated(got, blocks, pb, n)
+
+
+def test_block_kv_checksums_scratch_larger_than_buffer():
+    """1000-byte keys sharing 990 bytes with their predecessor: the rebuilt keys
+    (the scratch kv_kernel reads them from) take over 20 times the bytes of the
+    buffer the blocks lie in, so a key bound by base_len fails"""
+    rng = np.random.default_rng(31)
+    blocks = []
+    for b in range(6):
+        key, ents = rng.integers(0, 256, 1000, dtype=np.uint8).tobytes(), []
+        for j in range(64):
+            key = key[:990] + rng.integers(0, 256, 10, dtype=np.uint8).tobytes()
+            ents.append((key, bytes([j]) * (j % 3)))
+        kind = (blockgen.DATA, blockgen.META, blockgen.INDEX | blockgen.FULL)[b % 3]
+        blocks.append((blockgen.build(ents, kind=kind, interval=64, share_over_restarts=True), kind))
+    offs = np.cumsum([3] + [len(b) + 5 for b, _ in blocks[:-1]]).astype(np.uint64)
+    sizes = np.array([len(b) for b, _ in blocks], np.uint32)
+    kinds = np.array([k for _, k in blocks], np.uint8)
+    base = np.zeros(int(offs[-1]) + int(sizes[-1]), np.uint8)
+    for o, (b, _) in zip(offs, blocks):
+        base[int(o):int(o) + len(b)] = np.frombuffer(b, np.uint8)
+    want = kvsites.restated_batch(blocks, 8)
+    assert int(want[0][-1]) == 6 * 64 and 1000 * 6 * 64 > 20 * len(base)
+    check_restated(run_blocks(d(base), offs, sizes, kinds, 8, 6 * 64), blocks, 8, "scratch")
+
+
+def test_block_kv_checksums_capacity():
+    """capacity == total succeeds; total - 1 raises with the needed total and
+    stores no checksum or protection value; a batch without keys succeeds with
+    capacity 0"""
+    from forst_amd import ForstError
+
+    base, offs, sizes, kinds, blocks = random_batch()
+    n = 700
+    offs, sizes, kinds, blocks = offs[:n], sizes[:n], kinds[:n], blocks[:n]
+    want = kvsites.restated_batch(blocks, 4)
+    total = int(want[0][-1])
+    g = d(base)
+    check_restated(run_blocks(g, offs, sizes, kinds, 4, total), blocks, 4, "capacity == total")
+    with pytest.raises(ForstError) as ei:
+        run_blocks(g, offs, sizes, kinds, 4, total - 1)
+    assert f"< {total} keys" in str(ei.value)
+    enc, prot, first, status = ei.value.outputs
+    assert (enc == S8).all() and (prot.view(np.uint64) == S64).all()
+    # first_key and status are expected to be written: the count pass that
+    # finds the needed total fills them before the capacity is checked
+    same(first[:n + 1], want[0], ("capacity - 1", "first_key"))
+    same(status[:n], want[1], ("capacity - 1", "status"))
+    assert (first[n + 1:] == S64).all() and (status[n:] == S8).all()
+    # no keys at all: blocks without restarts, damaged blocks, descriptors past the buffer
+    _, o2, s2, k2, all_blocks = random_batch()
+    none = [j for j, b in enumerate(all_blocks)
+            if b is None or kvsites.restated_batch([b], 4)[0][-1] == 0][:300]
+    blocks0 = [all_blocks[j] for j in none]
+    assert len(blocks0) == 300
+    got = run_blocks(g, o2[none], s2[none], k2[none], 4, 0)
+    check_restated(got, blocks0, 4, "no keys")
+    assert len(got[0]) == 0 and len(got[1]) == 0 and (got[2] == 0).all()
+
+
+def test_write_batch_long_varints():
+    """WriteBatch reps with a 3-byte length and 3..5-byte column family varints
+    (kv_blocks), answered by the reference's WriteBatch::Iterate"""
+    base, offs, lens, reps = kvsites.write_batch_case(*kvsites.kv_blocks())
+    prot, first, st, nprot = engine.write_batch_protect_batch(
+        d(base), d(offs.view(np.int64)), d(lens.view(np.int32)))
+    prot, first, st, nprot = host(prot).view(np.uint64), host(first), host(st), host(nprot)
+    for j, (name, status, want) in enumerate(reps):
+        assert O.WB_STATUS[int(st[j])] == status, name
+        got = prot[first[j]:first[j] + nprot[j]]
+        assert got.tolist() == [int(x) for x in want], name
+        code, owant = O.write_batch_protect(base[int(offs[j]):int(offs[j]) + int(lens[j])].tobytes())
+        assert code == int(st[j]) and owant == got.tolist(), name

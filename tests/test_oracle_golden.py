@@ -247,3 +247,60 @@ def test_oracle_write_batch_vs_reference(kv_sites):
         code, got = O.write_batch_protect(base[int(o):int(o) + int(n)].tobytes())
         assert O.WB_STATUS[code] == status, name
         assert [int(x) for x in prot] == got, name
+
+
+def _check_block_restatement(base, offs, sizes, kinds, cases, pbs):
+    reached = 0
+    for j, c in enumerate(cases):
+        blk = base[int(offs[j]):int(offs[j]) + int(sizes[j])].tobytes()
+        name = c.get("name") or (c["src"], c["kind_name"])
+        for pb in pbs:
+            st, nk, enc, prot = O.block_kv_checksums(blk, int(kinds[j]), pb)
+            want = c[f"keys_{pb}"]
+            if want < 0:  # the reference's size_ = 0 error marker
+                assert st in (1, 2) and nk == 0 and enc == b"", (name, pb, st, nk)
+                continue
+            assert st == 0 and nk == want, (name, pb, st, nk, want)
+            assert enc.hex() == c[f"kv_checksum_{pb}"], (name, pb)
+            assert prot.view(np.uint8).reshape(-1, 8)[:, :pb].tobytes() == enc
+            reached += nk
+    return reached
+
+
+def test_oracle_block_kv_checksums_vs_reference(kv_sites):
+    """the restatement of Block::Initialize{Data,Index,MetaIndex}BlockProtectionInfo
+    (block.cc:1113-1235) reproduces the reference on every block cut from the
+    reference-written SSTs and on the damaged ones: key count or error marker,
+    every kv_checksum_ byte"""
+    import kvsites
+
+    base, offs, sizes, kinds, cases = kvsites.block_case(*kv_sites)
+    assert len(cases) == 117
+    assert _check_block_restatement(base, offs, sizes, kinds, cases, (8, 2)) == 2 * 1559
+
+
+def test_oracle_block_kv_checksums_vs_reference_crafted():
+    """... and on the crafted blocks of kv_blocks (multi-byte varints, hash
+    index geometry, 64 KiB blocks, first keys, in-bounds damage), protection
+    bytes 1, 2, 4 and 8"""
+    import kvsites
+
+    base, offs, sizes, kinds, cases = kvsites.block_case(*kvsites.kv_blocks())
+    assert len(cases) >= 78
+    assert _check_block_restatement(base, offs, sizes, kinds, cases, (1, 2, 4, 8)) > 0
+    by_name = {c["name"]: c for c in cases}
+    assert by_name["bit31_65537"]["keys_8"] == -1 and by_name["plain_65537"]["keys_8"] > 0
+    assert by_name["hash_exactly_65536"]["size"] == 65536
+
+
+def test_oracle_write_batch_vs_reference_long_varints():
+    """WriteBatch reps with a 3-byte length and 3..5-byte column family varints
+    (kv_blocks), answered by the reference's WriteBatch::Iterate"""
+    import kvsites
+
+    base, offs, lens, reps = kvsites.write_batch_case(*kvsites.kv_blocks())
+    assert len(reps) >= 6
+    for (name, status, prot), o, n in zip(reps, offs, lens):
+        code, got = O.write_batch_protect(base[int(o):int(o) + int(n)].tobytes())
+        assert O.WB_STATUS[code] == status, name
+        assert [int(x) for x in prot] == got, name
