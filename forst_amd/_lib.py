@@ -15,7 +15,7 @@ _lib = None
 
 
 class ForstError(RuntimeError):
-    pass
+    code = None  # the FORST_E* return code of the failed call (check())
 
 
 def build(jobs=8):
@@ -122,8 +122,13 @@ def lib():
     return L
 
 
-def check(rc):
+def check(rc, **info):
+    """raises ForstError (code = rc, and info's items as further attributes)
+    unless rc is FORST_OK"""
     if rc != 0:
         msg = lib().forst_last_error().decode(errors="replace")
-        raise ForstError(f"forst call failed ({rc}): {msg}")
+        err = ForstError(f"forst call failed ({rc}): {msg}")
+        err.code = rc
+        vars(err).update(info)
+        raise err
     return rc

@@ -212,18 +212,34 @@ def wal_record_crc_batch(log, header_offsets, write_in_place=True, out=None, str
     return out
 
 
-def wal_record_xxh3_batch(log, header_offsets, stream=None):
+def _out(t, n, size):
+    """a caller's output tensor: on the device, contiguous, `size`-byte
+    integers, at least n of them"""
+    assert t.is_cuda and t.is_contiguous() and not t.dtype.is_floating_point
+    assert t.element_size() == size and t.numel() >= n, (t.dtype, t.numel(), n)
+    return t
+
+
+def wal_record_xxh3_batch(log, header_offsets, stream=None, hashes=None, first=None):
     """XXH3_64bits per logical record (log_reader.cc:95-165).  Returns
-    (hashes int64 [n_logical], first physical record index [n_logical])."""
+    (hashes int64 [n_logical], first physical record index [n_logical]).
+    hashes / first: the caller's own output tensors (64-bit, n_phys entries);
+    first=False passes NULL for first_phys (None is returned for it)."""
     _dev_u8(log)
     n = header_offsets.numel()
-    hashes = torch.empty(max(n, 1), dtype=torch.int64, device=log.device)
-    first = torch.empty(max(n, 1), dtype=torch.int64, device=log.device)
+    if hashes is None:
+        hashes = torch.empty(max(n, 1), dtype=torch.int64, device=log.device)
+    if first is None:
+        first = torch.empty(max(n, 1), dtype=torch.int64, device=log.device)
+    _out(hashes, n, 8)
+    if first is not False:
+        _out(first, n, 8)
     nl = ctypes.c_uint64()
     check(lib().forst_wal_record_xxh3_batch(log.data_ptr(), log.numel(), header_offsets.data_ptr(),
-                                            n, hashes.data_ptr(), first.data_ptr(),
+                                            n, hashes.data_ptr(),
+                                            None if first is False else first.data_ptr(),
                                             ctypes.byref(nl), _stream(stream)))
-    return hashes[:nl.value], first[:nl.value]
+    return hashes[:nl.value], None if first is False else first[:nl.value]
 
 
 class WalRecords(ctypes.Structure):
@@ -268,38 +284,70 @@ def _recover_sig(L):
                       vp, vp]
 
 
+WAL_RECORD_FIELDS = (("offset", 8), ("length", 8), ("hash", 8), ("n_fragments", 4))
+WAL_REPORT_FIELDS = (("offset", 8), ("bytes", 8), ("reason", 4), ("type", 4))
+
+
+def _wal_members(given, fields, capacity, dev):
+    """the tensors behind one of forst_wal_recover_batch's output structs ->
+    (dict with every member; None = a NULL member, capacity).  given: None (the
+    wrapper allocates `capacity` entries) or the caller's dict."""
+    if given is None:
+        return {k: torch.empty(capacity, dtype=torch.int64 if size == 8 else torch.int32,
+                               device=dev) for k, size in fields}, capacity
+    assert set(given) <= {k for k, _ in fields}, sorted(given)
+    out = {k: given.get(k) for k, _ in fields}
+    held = [t.numel() for t in out.values() if t is not None]
+    if capacity is None:
+        capacity = min(held) if held else 0
+    for k, size in fields:
+        if out[k] is not None:
+            _out(out[k], capacity, size)
+    return out, capacity
+
+
 def wal_recover_batch(log, log_number=0, mode=kPointInTimeRecovery, record_capacity=None,
-                      report_capacity=1024, stream=None):
+                      report_capacity=None, stream=None, records=None, reports=None, retry=True):
     """log::Reader::ReadRecord over a whole device log image (log_reader.cc:69-320):
     returns (records dict of device tensors offset/length/hash/n_fragments,
-    reports dict of device tensors offset/bytes/reason/type, result)."""
+    reports dict of device tensors offset/bytes/reason/type, result).
+    records / reports: the caller's own output tensors by member name; a member
+    that is missing or None is passed as NULL (and returned as None).
+    record_capacity / report_capacity may be smaller than those tensors; left
+    out, they are what the tensors hold (without tensors: log bytes / 1024 and
+    1024).  A call that comes back truncated is repeated with arrays of the
+    reported counts -- for the arrays the wrapper allocated, and unless
+    retry=False, which returns the call's result as it is: the tensors
+    unsliced, result.truncated set."""
     _dev_u8(log)
     _recover_sig(lib())
-    if record_capacity is None:
+    dev = log.device
+    if records is None and record_capacity is None:
         record_capacity = max(1024, log.numel() // 1024)
+    if reports is None and report_capacity is None:
+        report_capacity = 1024
     while True:
-        dev = log.device
-        rec = {"offset": torch.empty(record_capacity, dtype=torch.int64, device=dev),
-               "length": torch.empty(record_capacity, dtype=torch.int64, device=dev),
-               "hash": torch.empty(record_capacity, dtype=torch.int64, device=dev),
-               "n_fragments": torch.empty(record_capacity, dtype=torch.int32, device=dev)}
-        rep = {"offset": torch.empty(report_capacity, dtype=torch.int64, device=dev),
-               "bytes": torch.empty(report_capacity, dtype=torch.int64, device=dev),
-               "reason": torch.empty(report_capacity, dtype=torch.int32, device=dev),
-               "type": torch.empty(report_capacity, dtype=torch.int32, device=dev)}
+        rec, record_capacity = _wal_members(records, WAL_RECORD_FIELDS, record_capacity, dev)
+        rep, report_capacity = _wal_members(reports, WAL_REPORT_FIELDS, report_capacity, dev)
         res = WalRecoverResult()
         check(lib().forst_wal_recover_batch(
             log.data_ptr(), log.numel(), log_number, mode,
-            WalRecords(*[rec[k].data_ptr() for k in ("offset", "length", "hash", "n_fragments")]),
-            record_capacity,
-            WalReports(*[rep[k].data_ptr() for k in ("offset", "bytes", "reason", "type")]),
-            report_capacity, ctypes.byref(res), _stream(stream)))
-        if not res.truncated:
+            WalRecords(*[_p(rec[k]) for k, _ in WAL_RECORD_FIELDS]), record_capacity,
+            WalReports(*[_p(rep[k]) for k, _ in WAL_REPORT_FIELDS]), report_capacity,
+            ctypes.byref(res), _stream(stream)))
+        grow_rec = records is None and res.n_records > record_capacity
+        grow_rep = reports is None and res.n_reports > report_capacity
+        if not retry or not (grow_rec or grow_rep):
             break
-        record_capacity = max(record_capacity, res.n_records)
-        report_capacity = max(report_capacity, res.n_reports)
-    rec = {k: v[:res.n_records] for k, v in rec.items()}
-    rep = {k: v[:res.n_reports] for k, v in rep.items()}
+        if grow_rec:
+            record_capacity = res.n_records
+        if grow_rep:
+            report_capacity = res.n_reports
+    if not retry:
+        return rec, rep, res
+    nr, np_ = min(res.n_records, record_capacity), min(res.n_reports, report_capacity)
+    rec = {k: None if v is None else v[:nr] for k, v in rec.items()}
+    rep = {k: None if v is None else v[:np_] for k, v in rep.items()}
     return rec, rep, res
 
 
@@ -385,33 +433,49 @@ def memtable_protect_batch(base, entry_offsets, protection_bytes, write_in_place
     return o, s
 
 
-def write_batch_protect_batch(base, rep_offsets, rep_sizes, capacity=None, stream=None):
+def write_batch_protect_batch(base, rep_offsets, rep_sizes, capacity=None, stream=None, prot=None,
+                              first_entry=None, status=None, n_protected=None):
     """WriteBatchInternal::UpdateProtectionInfo per WriteBatch rep
     (db/write_batch.cc:3164-3181), parsed on the device.  Returns
     (prot, first_entry, status, n_protected): rep b's protection values are
-    prot[first_entry[b]:first_entry[b+1]].  Synchronous (one count read-back)."""
+    prot[first_entry[b]:first_entry[b+1]].  Synchronous (one count read-back).
+    prot / first_entry / status / n_protected: the caller's own output tensors
+    (u64[capacity], i64[n + 1], u8[n], i32[n]); status=False / n_protected=False
+    pass NULL (None is returned for them).  With prot given and no capacity,
+    the capacity is what prot holds.  A capacity below the total raises a
+    ForstError whose n_total is the capacity to call again with."""
     _dev_u8(base)
     n = _desc(rep_offsets, rep_sizes)
     dev = base.device
-    first = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    status = torch.empty(n, dtype=torch.uint8, device=dev)
-    nprot = torch.empty(n, dtype=torch.int32, device=dev)
+    first = first_entry
+    if first is None:
+        first = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    _out(first, n + 1, 8)
+    if status is None:
+        status = torch.empty(n, dtype=torch.uint8, device=dev)
+    if n_protected is None:
+        n_protected = torch.empty(n, dtype=torch.int32, device=dev)
+    st = None if status is False else _out(status, n, 1)
+    nprot = None if n_protected is False else _out(n_protected, n, 4)
     total = ctypes.c_uint64()
+    args = (base.data_ptr(), base.numel(), rep_offsets.data_ptr(), rep_sizes.data_ptr(), n,
+            first.data_ptr())
+    if capacity is None and prot is not None:
+        capacity = prot.numel()
     if capacity is None:  # size from the header counts: a first call with capacity 0
-        rc = lib().forst_write_batch_protect_batch(base.data_ptr(), base.numel(),
-                                                   rep_offsets.data_ptr(), rep_sizes.data_ptr(),
-                                                   n, first.data_ptr(), None, 0, None, None,
+        rc = lib().forst_write_batch_protect_batch(*args, None, 0, None, None,
                                                    ctypes.byref(total), _stream(stream))
         if rc != 0 and total.value == 0:
             check(rc)
         capacity = total.value
-    prot = torch.empty(max(1, capacity), dtype=torch.uint64, device=dev)
-    check(lib().forst_write_batch_protect_batch(base.data_ptr(), base.numel(),
-                                                rep_offsets.data_ptr(), rep_sizes.data_ptr(), n,
-                                                first.data_ptr(), prot.data_ptr(), capacity,
-                                                status.data_ptr(), nprot.data_ptr(),
-                                                ctypes.byref(total), _stream(stream)))
-    return prot[:total.value], first, status, nprot
+    if prot is None:
+        prot = torch.empty(max(1, capacity), dtype=torch.uint64, device=dev)
+    _out(prot, capacity, 8)
+    rc = lib().forst_write_batch_protect_batch(*args, prot.data_ptr(), capacity, _p(st),
+                                               _p(nprot), ctypes.byref(total), _stream(stream))
+    check(rc, n_total=total.value)
+    return prot[:total.value], first[:n + 1], st if st is None else st[:n], \
+        nprot if nprot is None else nprot[:n]
 
 
 class BlockKind(enum.IntFlag):

@@ -265,6 +265,25 @@ def memtable_protect(base, offs, prot_bytes):
     return b.copy(), out, st
 
 
+def write_batch_protect_into(base, offs, lens, capacity, prot, first, status, n_protected):
+    """one forst_write_batch_protect_batch call into the caller's arrays (prot
+    u64, first u64[n + 1], status u8[n] or None, n_protected u32[n] or None;
+    None = NULL) with the given capacity -> (return code, *n_total)"""
+    base = _aligned(base)
+    offs = np.ascontiguousarray(offs, np.uint64)
+    lens = np.ascontiguousarray(lens, np.uint32)
+    n = len(offs)
+    assert prot.dtype == np.uint64 and len(prot) >= capacity
+    assert first.dtype == np.uint64 and len(first) >= n + 1
+    assert status is None or (status.dtype == np.uint8 and len(status) >= n)
+    assert n_protected is None or (n_protected.dtype == np.uint32 and len(n_protected) >= n)
+    total = ctypes.c_uint64()
+    rc = lib().forst_write_batch_protect_batch(_p(base), base.nbytes, _p(offs), _p(lens), n,
+                                               _p(first), _p(prot), capacity, _p(status),
+                                               _p(n_protected), ctypes.byref(total), None)
+    return rc, total.value
+
+
 def write_batch_protect(base, offs, lens):
     """-> (prot, first_entry, status, n_protected)"""
     base = _aligned(base)
@@ -307,24 +326,38 @@ def block_kv_checksum(base, offs, sizes, kinds, pb):
     return enc[:m * pb], prot[:m], first, st
 
 
-def wal_recover(log, log_number=0, mode=2, cap=None):
+def wal_recover(log, log_number=0, mode=2, cap=None, rep_cap=None, records=None, reports=None):
     """forst_wal_recover_batch on the SIMT emulator: (records, reports, result)
     with records = (offset, length, hash, n_fragments) arrays, reports =
-    (offset, bytes, reason, type) arrays"""
+    (offset, bytes, reason, type) arrays.  cap / rep_cap: the record / report
+    capacity (rep_cap defaults to cap).  records / reports: the caller's own
+    4-tuples of arrays (u64, u64, u64, u32), None for a NULL member, with
+    explicit capacities; they are returned as they are, not sliced."""
     from forst_amd.engine import WalRecords, WalReports, WalRecoverResult, _recover_sig
     L = lib()
     _recover_sig(L)
     log = _aligned(log)
-    cap = cap or max(64, log.nbytes // 7 + 2)
-    ro, rl, rh = (np.zeros(cap, np.uint64) for _ in range(3))
-    rn = np.zeros(cap, np.uint32)
-    po, pb = np.zeros(cap, np.uint64), np.zeros(cap, np.uint64)
-    pr, pt = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32)
+    if cap is None:
+        assert records is None
+        cap = max(64, log.nbytes // 7 + 2)
+    if rep_cap is None:
+        assert reports is None
+        rep_cap = cap
+    own = records is None and reports is None
+    if records is None:
+        records = tuple(np.zeros(cap, t) for t in (np.uint64, np.uint64, np.uint64, np.uint32))
+    if reports is None:
+        reports = tuple(np.zeros(rep_cap, t) for t in (np.uint64, np.uint64, np.uint32, np.uint32))
+    for arrs, n in ((records, cap), (reports, rep_cap)):
+        for a, size in zip(arrs, (8, 8, 8, 4) if arrs is records else (8, 8, 4, 4)):
+            assert a is None or (a.itemsize == size and len(a) >= n and a.flags.c_contiguous)
     res = WalRecoverResult()
     rc = L.forst_wal_recover_batch(_p(log), log.nbytes, log_number, mode,
-                                   WalRecords(_p(ro), _p(rl), _p(rh), _p(rn)), cap,
-                                   WalReports(_p(po), _p(pb), _p(pr), _p(pt)), cap,
+                                   WalRecords(*[_p(a) for a in records]), cap,
+                                   WalReports(*[_p(a) for a in reports]), rep_cap,
                                    ctypes.byref(res), None)
     _chk(rc)
-    n, m = res.n_records, res.n_reports
-    return (ro[:n], rl[:n], rh[:n], rn[:n]), (po[:m], pb[:m], pr[:m], pt[:m]), res
+    if not own:
+        return records, reports, res
+    n, m = min(res.n_records, cap), min(res.n_reports, rep_cap)
+    return tuple(a[:n] for a in records), tuple(a[:m] for a in reports), res

@@ -5,8 +5,6 @@ reference-made fixtures (tests/golden/gen_kv_golden.py: the reference's own
 MemTable::Add / VerifyEntryChecksum and WriteBatch::Iterate) and, at full size,
 compared entry for entry with the oracle (itself pinned to those fixtures by
 tests/test_oracle_golden.py)."""
-import struct
-
 import numpy as np
 import pytest
 
@@ -151,39 +149,11 @@ def test_write_batch_fixtures(kv_sites):
             assert len(got) == len(want) == first[j + 1] - first[j], name
 
 
-def _wb_rep(rng, nrec):
-    """a WriteBatch rep (write_batch.cc record layout) of nrec random records"""
-    out = bytearray(struct.pack("<QI", int(rng.integers(0, 2**56)), 0))
-    cnt = 0
-    for _ in range(nrec):
-        tag = int(rng.choice([0x01, 0x05, 0x00, 0x04, 0x07, 0x08, 0x02, 0x06, 0x0F, 0x0E, 0x11,
-                              0x10, 0x16, 0x17, 0x03, 0x0D]))
-        out.append(tag)
-        if tag in (0x05, 0x04, 0x08, 0x06, 0x0E, 0x10, 0x17):
-            cf = int(rng.integers(1, 300))
-            while cf >= 128:
-                out.append((cf & 127) | 128)
-                cf >>= 7
-            out.append(cf)
-        parts = {0x03: 1, 0x0D: 0, 0x00: 1, 0x04: 1, 0x07: 1, 0x08: 1}.get(tag, 2)
-        for p in range(parts):
-            ln = int(rng.integers(0, 300 if p == 0 else 1500))
-            v = ln
-            while v >= 128:
-                out.append((v & 127) | 128)
-                v >>= 7
-            out.append(v)
-            out += rng.integers(0, 256, ln, dtype=np.uint8).tobytes()
-        cnt += tag not in (0x03, 0x0D)
-    out[8:12] = struct.pack("<I", cnt)
-    return bytes(out)
-
-
 def test_write_batch_many_reps():
     """5000 reps of 0-40 records (recovery-shaped): every protection value and
     status against the oracle's restatement"""
     rng = np.random.default_rng(77)
-    reps = [_wb_rep(rng, int(rng.integers(0, 41))) for _ in range(5000)]
+    reps = [kvsites.wb_rep(rng, int(rng.integers(0, 41))) for _ in range(5000)]
     reps[7] = reps[7][:-1]  # truncated
     offs = np.cumsum([0] + [len(r) + int(rng.integers(0, 4)) for r in reps[:-1]]).astype(np.int64)
     base = np.zeros(int(offs[-1]) + len(reps[-1]) + 64, np.uint8)
