@@ -1,9 +1,22 @@
 // forst_amd/csrc/crc32c.hip -- CRC32C block kernels for gfx950 (CDNA4).
 //
 // Replaces, per block, util/crc32c.cc:1133 crc32c::Extend (SSE4.2 crc32c_3way
-// on the reference's x86 path) with one 64-lane wavefront per block.
+// on the reference's x86 path).  No carry-less multiply exists on CDNA4, so
+// CRC is table driven.  The file holds, in this order:
+//  * the v1 engine (wave_crc32c, fill_tables), one wavefront per block, which
+//    serves crc32c_block_kernel_simple: buffers shorter than one 4 KiB round;
+//  * the rows kernels (crc32c_rows_kernel<MODE>, crc32c_rows_raw_small_kernel,
+//    crc32c_rows_raw_filt_kernel), one block per 16-lane row: every other
+//    batch, in every mode;
+//  * crc32c_raw_lane_kernel, one message per lane: the short messages of a
+//    raw batch;
+//  * the launchers.  A batch of more descriptors than a rows launch indexes
+//    (FORST_ROWS_MAX_DESCS, engine.h) is split into several launches.
+// The rows and lane kernels' LDS table lookups (Lanes, look, g_then, step_k,
+// shift_at, ...) are in crc_lds.h, shared with the fused WAL-recovery kernel
+// of xxh3.hip; the tables themselves come from gen_tables.py.
 //
-// Algorithm (no carry-less multiply exists on CDNA4, so CRC is table driven):
+// The v1 algorithm:
 //  * A block's message is covered by R rounds of 4 KiB ending at a dword
 //    boundary W_end <= end; lane l owns the 64-byte segment [64l, 64l+64) of
 //    each round (4 x global_load_dwordx4 per lane).  Bytes in front of the
@@ -22,6 +35,7 @@
 // The combine constants are block-size independent, so mixed 4/16/64 KiB
 // batches run in one launch.  See DESIGN.md for the roofline analysis.
 #include "crc32c_tables.h"
+#include "crc_lds.h"
 #include "device_common.h"
 #include "engine.h"
 #include "stream_common.h"
@@ -205,113 +219,17 @@ __device__ __forceinline__ void fill_tables(uint32_t* L) {
 }
 
 // ---------------------------------------------------------------------------
-// Streaming block kernel v2: two independent CRC chains per lane.
-//
-// The latency of the v1 kernel is a serial chain of 17 dependent LDS table
-// steps per 4 KiB round (16 dwords + the hop) plus a 6-step combine tree per
-// block.  v2 halves the chain: in every 4 KiB round, chain c (0, 1) of lane l
-// owns the 32-byte segment [2048c + 32l, +32) -- 8 dwords -- so a lane runs
-// two independent 8-step chains whose LDS latencies overlap.  The hop to the
-// next round is fused with the first dword step (s' = J2(s) ^ G(w0), J2 = shift
-// by 4096 - 32 + 4 bytes).  The finish is three table steps deep instead of a
-// tree: every lane moves each chain state to the end of its 16-lane row with
-// A[lo] (lo = 15 - (l & 15)), the rows are XOR-reduced with DPP (no tables),
-// and the 8 row values (2 chains x 4 rows) are moved to the end of the round
-// with B[hi] and XORed.  The <= 3 tail bytes and the block's type byte are
-// folded in ONE slicing step of k <= 4 bytes.
-//
-// LDS (byte addresses; the only __shared__ object, at 0):
-//   [0, 64K)       G and J2, replicated 8x and interleaved: row e (256 B) holds
-//                  G_t[e] copy c at dword 8t + c and J2_t[e] copy c at dword
-//                  32 + 8t + c (t = 0..3 table, c = 0..7 copy).  Lane l
-//                  (c = l & 7, g = (l >> 3) & 3) does the i-th lookup of a
-//                  step on table i ^ g with byte i ^ g, so the 32 lanes of a
-//                  ds_read_b32 bank group hit dwords 8{0,1,2,3} + c: 32
-//                  distinct banks, conflict free.  The address
-//                  256 * byte + 4 (8 t + c) [+ 128 for J2] is ONE v_perm_b32 of
-//                  the data word and a per-lane constant.
+// The rows and lane kernels' tables (crc_lds.h has the layout of the first
+// 64 KiB and the lookups).  LDS byte addresses; the kernel's table array is
+// the __shared__ object at 0:
+//   [0, 64K)       G and the kernel's hop J, replicated 8x and interleaved
 //   [64K, 124K)    A[1..15]: shift by 32 lo bytes (unreplicated, 4 KiB each)
-//   [124K, 152K)   B[1..7]: shift by 512 hi bytes
+//   [124K, 128K)   B[1]: shift by 512 bytes
 // ---------------------------------------------------------------------------
+using namespace fcrc;
 constexpr uint32_t kOffA2 = 65536;
 constexpr uint32_t kOffB2 = kOffA2 + 15 * 4096;
-constexpr uint32_t kLds2Bytes = kOffB2 + 7 * 4096;
-static_assert(kLds2Bytes <= 160 * 1024, "v2 tables must fit in LDS");
-constexpr uint32_t kRB2 = FORST_CRC_ROUND_BYTES;
-constexpr uint32_t kSeg2 = FORST_CRC2_SEG_BYTES;       // 32
-constexpr uint32_t kChain2 = FORST_CRC2_CHAIN_BYTES;   // 2048
-static_assert(kSeg2 * 16 * 8 == 2 * kChain2, "A/B tables assume 32-byte segments, 2 chains");
-
-__device__ __forceinline__ uint32_t lds32(const uint8_t* __restrict__ Lb, uint32_t addr) {
-  return *reinterpret_cast<const uint32_t*>(Lb + addr);
-}
-
-struct Lanes2 {
-  uint32_t lpack;     // byte i: 4 (8 (i^g) + c)  (G; J2 is +128, folded into the ds_read offset)
-  uint32_t sel[4];    // v_perm selector: addr = {0, 0, x.b(i^g), lpack.b(i)}
-};
-
-__device__ __forceinline__ Lanes2 lanes2(uint32_t lane) {
-  Lanes2 k;
-  const uint32_t c = lane & 7, g = (lane >> 3) & 3;
-  k.lpack = 0;
-#pragma unroll
-  for (uint32_t i = 0; i < 4; ++i) {
-    const uint32_t tt = i ^ g;
-    k.lpack |= (4 * (8 * tt + c)) << (8 * i);
-    k.sel[i] = 0x0c0c0000u | ((4 + tt) << 8) | i;
-  }
-  return k;
-}
-__device__ __forceinline__ uint32_t lane_c4(uint32_t lane) { return (lane & 7) << 2; }
-
-// replicated 4-table linear map: G (J = false) or J2 (J = true)
-template <bool J>
-__device__ __forceinline__ uint32_t rep_map(const uint8_t* __restrict__ Lb, const Lanes2& k,
-                                            uint32_t x) {
-  uint32_t r = 0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    r ^= lds32(Lb, __builtin_amdgcn_perm(x, k.lpack, k.sel[i]) + (J ? 128u : 0u));
-  return r;
-}
-
-// k-byte slicing step (k <= 4, wave-uniform): the state after bytes y_0..y_k-1
-// (little-endian in y):  (s >> 8k) ^ XOR_j G[4-k+j][(s ^ y)_j]
-__device__ __forceinline__ uint32_t step_k(const uint8_t* __restrict__ Lb, const Lanes2& kk,
-                                           uint32_t s, uint32_t y, uint32_t k) {
-  if (k == 0) return s;
-  const uint32_t x = s ^ y;
-  const uint32_t c4 = lane_c4(threadIdx.x);
-  uint32_t r = k == 4 ? 0u : (s >> (8 * k));
-#pragma unroll
-  for (uint32_t j = 0; j < 4; ++j) {
-    if (j < k) {
-      const uint32_t t = 4 - k + j;
-      r ^= lds32(Lb, __builtin_amdgcn_perm(x, c4, 0x0c0c0000u | ((4 + j) << 8)) + 32 * t);
-    }
-  }
-  return r;
-}
-
-// linear shift through an unreplicated 4 x 256 table at byte offset b
-__device__ __forceinline__ uint32_t shift_at(const uint8_t* __restrict__ Lb, uint32_t b,
-                                             uint32_t v) {
-  return lds32(Lb, b + ((v & 0xffu) << 2)) ^ lds32(Lb, b + 1024 + (((v >> 8) & 0xffu) << 2)) ^
-         lds32(Lb, b + 2048 + (((v >> 16) & 0xffu) << 2)) ^ lds32(Lb, b + 3072 + ((v >> 24) << 2));
-}
-
-__device__ __forceinline__ void fill_tables2(uint32_t* L) {
-  const uint32_t tid = threadIdx.x;
-  // row e, dword d: d < 32 -> G_{d>>3}[e], else J2_{(d-32)>>3}[e]
-  for (uint32_t i = tid; i < 16384; i += kThreads) {
-    const uint32_t e = i >> 6, d = i & 63, t = (d >> 3) & 3;
-    L[i] = d < 32 ? kCrcG[t * 256 + e] : kCrcJ2[t * 256 + e];
-  }
-  for (uint32_t i = tid; i < 15 * 1024; i += kThreads) L[kOffA2 / 4 + i] = kCrcA[i];
-  for (uint32_t i = tid; i < 7 * 1024; i += kThreads) L[kOffB2 / 4 + i] = kCrcB[i];
-  __syncthreads();
-}
+constexpr uint32_t kSeg2 = FORST_CRC2_SEG_BYTES;  // 32: a lane's segment of a chain
 
 // raw mode with a per-message init: S0 = ~init moved back over m bytes
 __device__ __forceinline__ uint32_t unstep_m(uint32_t v, uint32_t m) {
@@ -322,322 +240,13 @@ __device__ __forceinline__ uint32_t unstep_m(uint32_t v, uint32_t m) {
   return r;
 }
 
-// wave-uniform description of one block, kept compact (three live copies
-// sit in SGPRs): derived quantities are recomputed where they are used
-struct Blk2 {
-  uint64_t off;
-  uint64_t we;  // window end: last dword boundary <= message end
-  uint32_t size, mod, extra, R, S0;
-  uint32_t pk;  // cA:1 | lA:6 | jA:3 | q:3 | nt:2 | valid:1 | slow:1 | m:2 | xtra:1
-  __device__ __forceinline__ uint32_t cA() const { return pk & 1u; }
-  __device__ __forceinline__ uint32_t lA() const { return (pk >> 1) & 63u; }
-  __device__ __forceinline__ uint32_t jA() const { return (pk >> 7) & 7u; }
-  __device__ __forceinline__ uint32_t q() const { return (pk >> 10) & 7u; }
-  __device__ __forceinline__ uint32_t nt() const { return (pk >> 13) & 3u; }
-  __device__ __forceinline__ bool valid() const { return (pk >> 15) & 1u; }
-  __device__ __forceinline__ bool slow() const { return (pk >> 16) & 1u; }
-  __device__ __forceinline__ uint32_t bm() const { return 0xffffffffu << (8 * ((pk >> 17) & 3u)); }
-  __device__ __forceinline__ bool xtra() const { return (pk >> 19) & 1u; }
-  // end of the round windows: the message's last dword boundary, one dword
-  // earlier for an xtra block
-  __device__ __forceinline__ uint64_t wend() const { return we - (xtra() ? 4u : 0u); }
-  // round-0 window start (may be < 0)
-  __device__ __forceinline__ int64_t w0() const {
-    return static_cast<int64_t>(wend()) - static_cast<int64_t>(R) * kRB2;
-  }
-};
-
-// Rounds of a window of d4 bytes (a dword multiple).  A window exactly one
-// dword longer than whole rounds -- a quarter of back-to-back 4 KiB blocks:
-// 4097 checksummed bytes starting at 3 mod 4 -- ends one dword early ("xtra");
-// that dword is one slicing step in the finish instead of an almost empty
-// round.  (Block modes only: raw messages of arbitrary lengths rarely hit it.)
-template <int MODE, uint32_t RB>
-__device__ __forceinline__ void window_rounds(uint64_t d4, uint32_t& R, bool& xtra) {
-  xtra = MODE != kModeRaw && (d4 & (RB - 1)) == 4 && d4 > RB;
-  R = static_cast<uint32_t>(xtra ? d4 / RB : (d4 + RB - 1) / RB);
-}
-
 template <int MODE>
 __device__ __forceinline__ bool mem_last_byte(const BlockArgs& a) {
   return MODE == kModeVerify || ((MODE == kModeCompute || MODE == kModeTrailer) && !a.last_bytes);
 }
 
-// scalar setup (blocks of the NEXT descriptor batch: at most two per batch,
-// reached by the look-ahead cursors before the batch becomes current)
-template <int MODE>
-__device__ __forceinline__ Blk2 blk2_setup_scalar(const BlockArgs& a, uint64_t k, uint64_t kend,
-                                                  uint64_t kb, const DescBatch& cb,
-                                                  const DescBatch& nb) {
-  Blk2 b;
-  const Desc d = batch_desc(k, kb, cb, nb);
-  b.off = d.off;
-  b.size = d.size;
-  b.mod = d.mod;
-  b.extra = d.extra;
-  const bool valid = k < kend && desc_in_range<MODE>(a, d);
-  const uint64_t E = b.off + b.size + (mem_last_byte<MODE>(a) ? 1u : 0u);
-  const uint64_t ws = b.off & ~3ull;
-  b.we = E & ~3ull;
-  const uint64_t d4 = b.we - ws;
-  bool xtra;
-  window_rounds<MODE, kRB2>(d4, b.R, xtra);
-  b.pk = xtra ? 1u << 19 : 0u;  // w0() below needs the flag
-  const uint32_t hA = static_cast<uint32_t>(static_cast<int64_t>(ws) - b.w0());
-  const uint32_t cA = hA >> 11, lA = (hA >> 5) & 63u, jA = (hA >> 2) & 7u;
-  // head segment starting in front of the buffer (only blocks at offset < 28):
-  // it is loaded from offset 0 and shifted up by q dwords in registers
-  const int64_t seg_head = static_cast<int64_t>(ws) - 4 * static_cast<int64_t>(jA);
-  const uint32_t q = seg_head < 0 ? static_cast<uint32_t>(-seg_head) >> 2 : 0u;
-  const uint32_t nt = static_cast<uint32_t>(E - b.we);
-  const uint32_t m = static_cast<uint32_t>(b.off & 3);
-  const bool slow = !valid || d4 < 64;
-  b.S0 = MODE == kModeRaw && a.init_crcs ? unstep_m(~b.extra, m) : kCrcS0[m];
-  if (slow) {  // the slow path loads on its own; dummy step loads at [0, 4 KiB)
-    b.we = kRB2;
-    b.R = 1;
-    b.pk = (nt << 13) | (valid ? 1u << 15 : 0u) | (1u << 16) | (m << 17);
-  } else {
-    b.pk = cA | (lA << 1) | (jA << 7) | (q << 10) | (nt << 13) | (valid ? 1u << 15 : 0u) |
-           (m << 17) | (xtra ? 1u << 19 : 0u);
-  }
-  return b;
-}
-
-// Per-lane derived block fields of the CURRENT descriptor batch (lane j <->
-// block kb + j), computed once per 64 blocks in vector code so that a block's
-// setup is a few v_readlane instead of ~100 scalar instructions.
-struct Derived2 {
-  uint32_t pk, R, S0;  // S0 only in raw mode (per-message init)
-};
-
-template <int MODE>
-__device__ __forceinline__ Derived2 derive2(const BlockArgs& a, const DescBatch& cb, uint64_t kb,
-                                            uint64_t kend, uint32_t lane) {
-  Derived2 d;
-  const uint64_t off = (static_cast<uint64_t>(cb.off_hi) << 32) | cb.off_lo;
-  const Desc ds{off, cb.size, cb.mod, cb.extra};
-  const bool valid = kb + lane < kend && desc_in_range<MODE>(a, ds);
-  const uint64_t E = off + cb.size + (mem_last_byte<MODE>(a) ? 1u : 0u);
-  const uint64_t ws = off & ~3ull;
-  const uint64_t we = E & ~3ull;
-  const uint64_t d4 = we - ws;
-  uint32_t R;
-  bool xtra;
-  window_rounds<MODE, kRB2>(d4, R, xtra);
-  const int64_t w0 = static_cast<int64_t>(we) - (xtra ? 4 : 0) - static_cast<int64_t>(R) * kRB2;
-  const uint32_t hA = static_cast<uint32_t>(static_cast<int64_t>(ws) - w0);
-  const uint32_t cA = hA >> 11, lA = (hA >> 5) & 63u, jA = (hA >> 2) & 7u;
-  const int64_t seg_head = static_cast<int64_t>(ws) - 4 * static_cast<int64_t>(jA);
-  const uint32_t q = seg_head < 0 ? static_cast<uint32_t>(-seg_head) >> 2 : 0u;
-  const uint32_t nt = static_cast<uint32_t>(E - we);
-  const uint32_t m = static_cast<uint32_t>(off & 3);
-  const bool slow = !valid || d4 < 64;
-  d.R = slow ? 1u : R;
-  d.pk = slow ? ((nt << 13) | (valid ? 1u << 15 : 0u) | (1u << 16) | (m << 17))
-              : (cA | (lA << 1) | (jA << 7) | (q << 10) | (nt << 13) | (valid ? 1u << 15 : 0u) |
-                 (m << 17) | (xtra ? 1u << 19 : 0u));
-  d.S0 = MODE == kModeRaw ? (a.init_crcs ? unstep_m(~cb.extra, m) : kCrcS0[m]) : 0u;
-  return d;
-}
-
-template <int MODE>
-__device__ __forceinline__ Blk2 blk2_setup(const BlockArgs& a, uint64_t k, uint64_t kend,
-                                           uint64_t kb, const DescBatch& cb, const DescBatch& nb,
-                                           const Derived2& cd) {
-  if (k - kb >= kBatch) return blk2_setup_scalar<MODE>(a, k, kend, kb, cb, nb);
-  const uint32_t sl = static_cast<uint32_t>(k - kb);
-  Blk2 b;
-  b.off = readlane64(cb.off_lo, cb.off_hi, sl);
-  b.size = readlane32(cb.size, sl);
-  b.mod = readlane32(cb.mod, sl);
-  b.extra = readlane32(cb.extra, sl);
-  b.pk = readlane32(cd.pk, sl);
-  b.R = readlane32(cd.R, sl);
-  b.S0 = MODE == kModeRaw ? readlane32(cd.S0, sl) : kCrcS0[(b.pk >> 17) & 3u];
-  b.we = b.slow() ? kRB2 : ((b.off + b.size + (mem_last_byte<MODE>(a) ? 1u : 0u)) & ~3ull);
-  return b;
-}
-
-struct StepBuf2 {
-  uint32_t w[2][8];
-  uint32_t t0, t1, t2;  // t2: the xtra dword
-};
-
-template <int MODE>
-__device__ __forceinline__ void issue_step2(const uint8_t* __restrict__ base, uint32_t lane,
-                                            const Blk2& b, uint32_t r, StepBuf2& buf) {
-  const int64_t w0 = b.w0();
-  const uint32_t cA = b.cA(), lA = b.lA();
-#pragma unroll
-  for (uint32_t c = 0; c < 2; ++c) {
-    int64_t so = w0 + static_cast<int64_t>(r) * kRB2 + kChain2 * c + kSeg2 * lane;
-    if (r == 0) {
-      // segments wholly in front of the head: any safe in-message address
-      const bool pre = c < cA || (c == cA && lane < lA);
-      so = pre ? static_cast<int64_t>(b.we) - kSeg2 : so;
-      so = so < 0 ? 0 : so;
-    }
-    const uint8_t* sp = base + so;
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const u32x4a4 v = ld16_a4(sp + 16 * q);
-      buf.w[c][4 * q + 0] = v.x;
-      buf.w[c][4 * q + 1] = v.y;
-      buf.w[c][4 * q + 2] = v.z;
-      buf.w[c][4 * q + 3] = v.w;
-    }
-  }
-  // tail dword at we (holds the <= 3 tail bytes; in verify mode the stored
-  // checksum starts inside it or is the next dword); slow blocks: offset 0
-  const uint32_t nt = b.nt();
-  const uint64_t t0 = b.slow() ? 0 : (nt > 0 || MODE == kModeVerify) ? b.we : b.we - 4;
-  buf.t0 = ld4v(base + t0);
-  buf.t1 = MODE == kModeVerify ? ld4v(base + (b.slow() || nt == 0 ? t0 : t0 + 4)) : 0u;
-  buf.t2 = MODE != kModeRaw ? ld4v(base + (b.xtra() ? b.we - 4 : t0)) : 0u;
-}
-
-__device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
-  return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);  // v_bitop3_b32: a ^ b ^ c
-}
-
-// the four table reads of G(x) (J = false) or J2(x) (J = true)
-template <bool J>
-__device__ __forceinline__ void rep_look(const uint8_t* __restrict__ Lb, const Lanes2& k,
-                                         uint32_t x, uint32_t (&l)[4]) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    l[i] = lds32(Lb, __builtin_amdgcn_perm(x, k.lpack, k.sel[i]) + (J ? 128u : 0u));
-}
-
-// G(x) ^ e: the next chain input when e is the next data word
-__device__ __forceinline__ uint32_t g_then(const uint8_t* __restrict__ Lb, const Lanes2& k,
-                                           uint32_t x, uint32_t e) {
-  uint32_t l[4];
-  rep_look<false>(Lb, k, x, l);
-  return xor3(l[0], l[1], xor3(l[2], l[3], e));
-}
-
-// one round of both chains.  Chain inputs are carried as x = state ^ next word,
-// so every step is 4 v_perm + 4 ds_read + 2 v_bitop3.
-__device__ __forceinline__ void stream_round2(const uint8_t* __restrict__ Lb, const Lanes2& K,
-                                              uint32_t lane, const Blk2& b, uint32_t r,
-                                              uint32_t (&s)[2], const uint32_t (&w)[2][8]) {
-  if (r == 0) {
-    const uint32_t cA = b.cA(), lA = b.lA(), jA = b.jA(), q = b.q();
-    const uint32_t bm = b.bm();
-#pragma unroll
-    for (uint32_t c = 0; c < 2; ++c) {
-      uint32_t wc[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) wc[j] = w[c][j];
-      if (q != 0 && c == cA) {  // head segment loaded from offset 0: shift up q dwords
-        uint32_t sh[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          uint32_t v = 0;
-#pragma unroll
-          for (int qq = 1; qq < 8; ++qq)
-            if (qq <= j) v = (q == static_cast<uint32_t>(qq)) ? wc[j - qq] : v;
-          sh[j] = v;
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) wc[j] = lane == lA ? sh[j] : wc[j];
-      }
-      // words in front of the message's first dword are zeroed (G(0) = 0, so
-      // the chain state stays 0 until the head word) ...
-      const uint32_t js = (c < cA || (c == cA && lane < lA)) ? 8u
-                          : (c == cA && lane == lA)          ? jA
-                                                             : 0u;
-#pragma unroll
-      for (uint32_t j = 0; j < 8; ++j) wc[j] = j < js ? 0u : wc[j];
-      // ... and the head word of the head lane loses the bytes in front of
-      // the message and gains S0 (uniform dynamic index jA)
-      if (c == cA) {
-        const uint32_t hv = wc[jA];
-        wc[jA] = lane == lA ? ((hv & bm) ^ b.S0) : hv;
-      }
-      uint32_t x = wc[0];
-#pragma unroll
-      for (int j = 1; j < 8; ++j) x = g_then(Lb, K, x, wc[j]);
-      s[c] = g_then(Lb, K, x, 0u);
-    }
-  } else {
-    // first word of each chain: J2(s) ^ G(w0) ^ w1 (hop fused with the step)
-    uint32_t x[2];
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      uint32_t lj[4], lg[4];
-      rep_look<true>(Lb, K, s[c], lj);
-      rep_look<false>(Lb, K, w[c][0], lg);
-      x[c] = xor3(xor3(lj[0], lj[1], lj[2]), xor3(lj[3], lg[0], lg[1]), xor3(lg[2], lg[3], w[c][1]));
-    }
-#pragma unroll
-    for (int j = 2; j < 8; ++j) {
-      x[0] = g_then(Lb, K, x[0], w[0][j]);
-      x[1] = g_then(Lb, K, x[1], w[1][j]);
-    }
-    s[0] = g_then(Lb, K, x[0], 0u);
-    s[1] = g_then(Lb, K, x[1], 0u);
-  }
-}
-
-// XOR of the 16 lanes of each row, valid in the row's last lane (DPP row_shr)
-template <int N>
-__device__ __forceinline__ uint32_t row_shr_xor(uint32_t v) {
-  return v ^ static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x110 + N,
-                                                               0xf, 0xf, false));
-}
-
-// XOR of the 16 lanes of each row, valid in every lane of the row (DPP row_ror)
-template <int N>
-__device__ __forceinline__ uint32_t row_ror_xor(uint32_t v) {
-  return v ^ static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x120 + N,
-                                                               0xf, 0xf, false));
-}
-
-// join the 2 x 64 chain states, fold in the tail bytes and the extra byte;
-// returns ~state (the crc32c::Extend value), wave-uniform
-template <int MODE>
-__device__ __forceinline__ uint32_t stream_finish2(const uint8_t* __restrict__ Lb,
-                                                   const Lanes2& K, uint32_t lane, const Blk2& b,
-                                                   const uint32_t (&s)[2], uint32_t t0,
-                                                   uint32_t t2, bool has_extra) {
-  // chain c of lane l ends 2048 (1 - c) + 32 (63 - l) bytes before the round end
-  const bool lo0 = (lane & 15) == 15;
-  const uint32_t abase = kOffA2 + 4096 * (14 - (lane & 15));  // A[lo], lo = 15 - (lane & 15)
-  uint32_t a0 = lo0 ? s[0] : shift_at(Lb, abase, s[0]);
-  uint32_t a1 = lo0 ? s[1] : shift_at(Lb, abase, s[1]);
-  a0 = row_shr_xor<1>(a0);
-  a1 = row_shr_xor<1>(a1);
-  a0 = row_shr_xor<2>(a0);
-  a1 = row_shr_xor<2>(a1);
-  a0 = row_shr_xor<4>(a0);
-  a1 = row_shr_xor<4>(a1);
-  a0 = row_shr_xor<8>(a0);
-  a1 = row_shr_xor<8>(a1);
-  // lane 16 rho + 15: chain 0 row value needs B[7 - rho], chain 1 B[3 - rho]
-  uint32_t v = 0;
-  if (lo0) {
-    const uint32_t rho = lane >> 4;
-    const uint32_t v0 = shift_at(Lb, kOffB2 + 4096 * (6 - rho), a0);
-    const uint32_t v1 = rho == 3 ? a1 : shift_at(Lb, kOffB2 + 4096 * (2 - rho), a1);
-    v = v0 ^ v1;
-  }
-  uint32_t st = readlane32(v, 15) ^ readlane32(v, 31) ^ readlane32(v, 47) ^ readlane32(v, 63);
-  if (MODE != kModeRaw && b.xtra()) st = step_k(Lb, K, st, t2, 4);
-  const uint32_t nt = b.nt();
-  uint32_t y = nt ? (t0 & (0xffffffffu >> (32 - 8 * nt))) : 0u;
-  uint32_t k = nt;
-  if (has_extra) {
-    y |= (b.extra & 0xffu) << (8 * k);
-    ++k;
-  }
-  return ~step_k(Lb, K, st, y, k);
-}
-
 // short messages (< 64 bytes past the head dword): dword-serial, wave-uniform
-__device__ __forceinline__ uint32_t small_crc2(const uint8_t* __restrict__ Lb, const Lanes2& K,
+__device__ __forceinline__ uint32_t small_crc2(const uint8_t* __restrict__ Lb, const Lanes& K,
                                                const uint8_t* p, uint32_t len, uint32_t init,
                                                uint32_t nextra, uint32_t extra) {
   uint32_t s = ~init;
@@ -657,158 +266,10 @@ __device__ __forceinline__ uint32_t small_crc2(const uint8_t* __restrict__ Lb, c
   return ~s;
 }
 
-// PROBE is always 0.  The parameter and the two probe arms of the round
-// dispatch below are what is left of the removed load-probe variants: without
-// those (never taken) arms the compiler orders one instruction of every
-// crc32c_stream2_kernel differently, and this kernel's code is to stay as it is.
-template <int MODE, int PROBE>
-__device__ __forceinline__ void crc32c_stream2_body(const BlockArgs& a) {
-  __shared__ uint32_t L[kLds2Bytes / 4];
-  fill_tables2(L);
-  const uint8_t* Lb = reinterpret_cast<const uint8_t*>(L);
-  const uint32_t lane = threadIdx.x & 63;
-  const uint32_t wave = uniform(threadIdx.x >> 6);
-  const Lanes2 K = lanes2(lane);
-  const uint64_t nw = static_cast<uint64_t>(gridDim.x) * kWaves;
-  const uint64_t gw = static_cast<uint64_t>(blockIdx.x) * kWaves + wave;
-  uint64_t kbeg, kend;
-  wave_share(a.n, nw, gw, kbeg, kend);
-  if (kbeg >= kend) return;
-  const bool has_extra = (MODE == kModeCompute || MODE == kModeTrailer) && a.last_bytes;
-
-  DescBatch cb, nb;
-  uint64_t kb = kbeg;
-  load_batch<MODE>(a, kb, kend, lane, cb);
-  load_batch<MODE>(a, kb + kBatch, kend, lane, nb);
-  Derived2 cd = derive2<MODE>(a, cb, kb, kend, lane);
-  // Three cursors over the (block, round) step sequence: C is computed from
-  // the buffer filled two steps ago, P1's loads are in flight, P2's are issued
-  // now -- two 4 KiB steps (8 KiB) per wave stay in flight while C computes.
-  uint64_t k = kbeg, k1 = 0, k2 = 0;  // blocks of C, P1, P2
-  uint32_t r = 0, r1 = 0, r2 = 0;     // their rounds
-  Blk2 C = blk2_setup<MODE>(a, k, kend, kb, cb, nb, cd);
-  Blk2 P1, P2;
-  auto advance = [&](const Blk2& b, uint64_t kk, uint32_t rr, Blk2& nbk, uint64_t& nk,
-                     uint32_t& nr) {
-    if (!b.slow() && rr + 1 < b.R) {
-      nbk = b;
-      nk = kk;
-      nr = rr + 1;
-    } else {
-      nk = kk + 1;
-      nr = 0;
-      nbk = blk2_setup<MODE>(a, nk, kend, kb, cb, nb, cd);
-    }
-  };
-  advance(C, k, 0, P1, k1, r1);
-  advance(P1, k1, r1, P2, k2, r2);
-  uint32_t rOut = 0, rSt = 0, rOk = 0;
-  StepBuf2 X, Y, Z;
-  issue_step2<MODE>(a.base, lane, C, 0, X);
-  issue_step2<MODE>(a.base, lane, P1, r1, Y);
-  uint32_t s[2] = {0, 0};
-
-  auto flush = [&](uint32_t cnt) {
-    const uint64_t i = kb + lane;
-    const bool mine = lane < cnt;
-    if (mine && a.out32) a.out32[i] = rOut;
-    if (MODE == kModeVerify) {
-      if (mine && a.stored_out) a.stored_out[i] = rSt;
-      if (mine && a.ok_out) a.ok_out[i] = static_cast<uint8_t>(rOk);
-      const uint64_t badm = __ballot(mine && rOk == 0);
-      if (a.mismatches && badm && lane == 0)
-        atomicAdd(a.mismatches, static_cast<unsigned long long>(__popcll(badm)));
-    }
-    if (MODE == kModeTrailer) {
-      if (mine && rOk) {
-        const uint64_t off = (static_cast<uint64_t>(cb.off_hi) << 32) | cb.off_lo;
-        uint8_t* p = a.base_w + off + cb.size;
-        if (a.last_bytes) p[0] = static_cast<uint8_t>(cb.extra);
-        stu32_bytes(p + 1, rOut);
-      }
-    }
-  };
-
-  // one step: issue P2 into nx, compute C from cu; false when done
-  auto step = [&](StepBuf2& cu, StepBuf2& nx) -> bool {
-    issue_step2<MODE>(a.base, lane, P2, r2, nx);
-    const bool last = C.slow() || r + 1 >= C.R;
-    if (PROBE == 1) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        s[0] ^= cu.w[0][j];
-        s[1] ^= cu.w[1][j];
-      }
-    } else if (PROBE == 3 && !C.slow()) {
-      stream_round2(Lb, K, lane, C, 1, s, cu.w);  // no head handling
-    } else if (!C.slow()) {
-      stream_round2(Lb, K, lane, C, r, s, cu.w);
-    }
-    if (last) {
-      uint32_t crc = 0, stored = 0;
-      if (!C.slow()) {
-        crc = stream_finish2<MODE>(Lb, K, lane, C, s, cu.t0, cu.t2, has_extra);
-        if (MODE == kModeVerify)
-          stored = C.nt() ? __builtin_amdgcn_alignbyte(cu.t1, cu.t0, C.nt()) : cu.t0;
-      } else if (C.valid()) {
-        const uint8_t* p = a.base + C.off;
-        const uint32_t init = MODE == kModeRaw ? C.extra : 0u;
-        crc = small_crc2(Lb, K, p, C.size + (mem_last_byte<MODE>(a) ? 1u : 0u), init, has_extra ? 1u : 0u, C.extra);
-        // retire(): keep the slow path's loads from merging into the hot path
-        if (MODE == kModeVerify) stored = retire(ldu32(p + C.size + 1));
-        crc = retire(crc);
-      }
-      uint32_t out, st = 0, ok = C.valid() ? 1u : 0u;
-      if (MODE == kModeRaw) {
-        out = crc;
-      } else if (MODE == kModeVerify) {
-        const uint32_t computed = crc_mask(crc);  // reader_common.cc:36-47
-        st = stored - C.mod;
-        ok = (C.valid() && st == computed) ? 1u : 0u;
-        out = computed;
-      } else {
-        out = crc_mask(crc) + C.mod;  // format.cc:594-600 + builder.cc:1340-1345
-      }
-      if (!C.valid()) {
-        out = 0;
-        st = 0;
-      }
-      const uint32_t kk = static_cast<uint32_t>(k - kb);
-      rOut = lane == kk ? out : rOut;
-      rSt = lane == kk ? st : rSt;
-      rOk = lane == kk ? ok : rOk;
-      if (k + 1 - kb == kBatch || k + 1 == kend) {
-        flush(static_cast<uint32_t>(k + 1 - kb));
-        if (k + 1 == kend) return false;
-        kb = k + 1;
-        cb = nb;
-        cd = derive2<MODE>(a, cb, kb, kend, lane);
-        load_batch<MODE>(a, kb + kBatch, kend, lane, nb);
-      }
-    }
-    // rotate the cursors: C <- P1 <- P2 <- the step after P2
-    C = P1;
-    k = k1;
-    r = r1;
-    P1 = P2;
-    k1 = k2;
-    r1 = r2;
-    advance(P1, k1, r1, P2, k2, r2);
-    return true;
-  };
-  while (step(X, Z) && step(Y, X) && step(Z, Y)) {
-  }
-}
-
-template <int MODE>
-__global__ void __launch_bounds__(kThreads) crc32c_stream2_kernel(BlockArgs a) {
-  crc32c_stream2_body<MODE, 0>(a);
-}
-
 // ---------------------------------------------------------------------------
 // CRC32C rows kernel (v3): one block per 16-lane row.
 //
-// In the one-block-per-wave kernels every block pays a full-wave finish
+// In a one-block-per-wave kernel every block pays a full-wave finish
 // (row-end shifts, DPP reduction, round-end shifts, tail step), a head set-up
 // and a scalar block set-up; for 4 KiB blocks that is a third of the work.
 // Here row r (lanes 16r..16r+15) owns a block and walks it in 1 KiB rounds:
@@ -824,7 +285,7 @@ __global__ void __launch_bounds__(kThreads) crc32c_stream2_kernel(BlockArgs a) {
 // word, with rows at round 0 and rows in the middle of a block running the
 // same code (J3(0) = 0).
 //
-// LDS: [0, 64K) G and J3 interleaved as in the v2 kernel, [64K, 124K) A[1..15],
+// LDS: [0, 64K) G and J3 interleaved (crc_lds.h), [64K, 124K) A[1..15],
 // [124K, 128K) B[1].
 // ---------------------------------------------------------------------------
 // block-mode results are staged in LDS and stored after the loop, not as rows
@@ -1052,7 +513,7 @@ __device__ __forceinline__ void crc32c_rows_body(const BlockArgs& a) {
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t wave = uniform(threadIdx.x >> 6);
   const uint32_t t = lane & 15;
-  const Lanes2 K = lanes2(lane);
+  const Lanes K = lanes(lane);
   __shared__ uint32_t s0t[4];  // head states by start alignment (a select, not branches)
   if (threadIdx.x < 4) s0t[threadIdx.x] = kCrcS0[threadIdx.x];
   __syncthreads();
@@ -1061,7 +522,8 @@ __device__ __forceinline__ void crc32c_rows_body(const BlockArgs& a) {
   const bool has_extra = (MODE == kModeCompute || MODE == kModeTrailer) && a.last_bytes;
 
   // descriptor batches from the work feed: lane j <-> descriptor cg + j (cb),
-  // ng + j (nb); a row's rel is the descriptor's global index (n < 2^32 - 1)
+  // ng + j (nb); a row's rel is the descriptor's index in the launch (n <=
+  // FORST_ROWS_MAX_DESCS, engine.h)
   BatchFeed feed;
   // block modes: the workgroup feed in 4-descriptor batches (one block per
   // row; A/B against 8: C2 verify +2.2 %, write +1.8 %, NS16 +0.9 %, C4
@@ -1241,8 +703,8 @@ __device__ __forceinline__ void crc32c_rows_body(const BlockArgs& a) {
 #pragma unroll
       for (int c = 0; c < 2; ++c) {
         uint32_t lj[4], lg[4];
-        rep_look<true>(Lb, K, r0 ? 0u : s[c], lj);
-        rep_look<false>(Lb, K, cu.w[c][0], lg);
+        look<true>(Lb, K, r0 ? 0u : s[c], lj);
+        look<false>(Lb, K, cu.w[c][0], lg);
         uint32_t x = xor3(xor3(lj[0], lj[1], lj[2]), xor3(lj[3], lg[0], lg[1]),
                           xor3(lg[2], lg[3], cu.w[c][1]));
 #pragma unroll
@@ -1277,8 +739,8 @@ __device__ __forceinline__ void crc32c_rows_body(const BlockArgs& a) {
           for (int j = 0; j < 8; ++j) wc[j] = (hl && q != 0) ? sh[j] : wc[j];
         }
         uint32_t lj[4], lg[4];
-        rep_look<true>(Lb, K, r0 ? 0u : s[c], lj);
-        rep_look<false>(Lb, K, hj == 0 ? ((wc[0] & bm) ^ S0) : wc[0], lg);
+        look<true>(Lb, K, r0 ? 0u : s[c], lj);
+        look<false>(Lb, K, hj == 0 ? ((wc[0] & bm) ^ S0) : wc[0], lg);
         uint32_t x = xor3(xor3(lj[0], lj[1], lj[2]), xor3(lj[3], lg[0], lg[1]),
                           xor3(lg[2], lg[3], wc[1]));
         x = hj == 1 ? ((wc[1] & bm) ^ S0) : x;
@@ -1481,7 +943,7 @@ constexpr uint32_t kLaneThreads = 512;
 // 16-byte loads of a short message: its bytes from the dword boundary in
 // front (m <= 3) plus the tail dword
 constexpr uint32_t kLaneChunks = (kRawSplit + 2 + 4 + 15) / 16;
-__device__ __forceinline__ uint32_t lane_raw_crc(const uint8_t* __restrict__ Lb, const Lanes2& K,
+__device__ __forceinline__ uint32_t lane_raw_crc(const uint8_t* __restrict__ Lb, const Lanes& K,
                                                  const uint8_t* base, uint64_t base_len,
                                                  uint64_t off, uint32_t n, uint32_t init,
                                                  bool has_init) {
@@ -1548,7 +1010,7 @@ __global__ void __launch_bounds__(kLaneThreads) crc32c_raw_lane_kernel(BlockArgs
   const uint8_t* Lb = reinterpret_cast<const uint8_t*>(L);
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t wave = uniform(threadIdx.x >> 6);
-  const Lanes2 K = lanes2(lane);
+  const Lanes K = lanes(lane);
   const uint64_t below = (1ull << lane) - 1;
   const uint64_t nw = static_cast<uint64_t>(gridDim.x) * kRawLaneWaves;
   constexpr uint64_t W = uint64_t(kRawLaneR) * 64;
@@ -1693,7 +1155,6 @@ namespace {
 enum class CrcKernel {
   kSimple,  // one wave per block: buffers shorter than one 4 KiB round
   kRows,    // one block per 16-lane row (crc32c_rows_kernel)
-  kV2,      // one block per wave, two chains per lane (crc32c_stream2_kernel)
 };
 
 hipError_t launch_kernel(void (*k)(BlockArgs), uint32_t grid, uint32_t threads, BlockArgs a,
@@ -1702,24 +1163,12 @@ hipError_t launch_kernel(void (*k)(BlockArgs), uint32_t grid, uint32_t threads, 
   return hipGetLastError();
 }
 
-// a rows-kernel launch with its work-feed counter (stream_common.h)
-hipError_t launch_fed(void (*k)(BlockArgs), uint32_t grid, uint32_t waves, BlockArgs b,
-                      hipStream_t s) {
-  hipError_t e = feed_setup(b, uint64_t(grid) * waves, s);
-  if (e != hipSuccess) return e;
-  e = launch_kernel(k, grid, 64 * waves, b, s);
-  const hipError_t f = scratch_free(b.ticket, s);
-  return e != hipSuccess ? e : f;
-}
-
 const char* crc_kernel_name(CrcKernel k, int mode) {
   static const char* const kNames[][4] = {
       {"crc32c_block_kernel_simple<compute>", "crc32c_block_kernel_simple<trailer>",
        "crc32c_block_kernel_simple<verify>", "crc32c_block_kernel_simple<raw>"},
       {"crc32c_rows_kernel<compute>", "crc32c_rows_kernel<trailer>", "crc32c_rows_kernel<verify>",
        "crc32c_rows_kernel<raw>"},
-      {"crc32c_stream2_kernel<compute>", "crc32c_stream2_kernel<trailer>",
-       "crc32c_stream2_kernel<verify>", "crc32c_stream2_kernel<raw>"},
   };
   return kNames[static_cast<int>(k)][mode & 3];
 }
@@ -1749,25 +1198,14 @@ hipError_t launch_crc_mode(CrcKernel k, const BlockArgs& a, uint32_t grid, hipSt
         if (e != hipSuccess) return e;
         return launch_fed(crc32c_rows_raw_filt_kernel, grid, kWaves, a, s);
       }
-    case CrcKernel::kV2:
-      return launch_kernel(crc32c_stream2_kernel<M>, grid, kThreads, a, s);
   }
   return hipErrorInvalidValue;
 }
 
-}  // namespace
-
-// raw CRCs of messages all under kRawSplit bytes: the lane kernel alone (a
-// longer one would be left out: the caller guarantees the lengths)
-hipError_t launch_crc32c_raw_lanes(const BlockArgs& a, hipStream_t stream) {
-  if (a.n == 0) return hipSuccess;
-  return launch_kernel(crc32c_raw_lane_kernel, 2 * device_info().num_cus, kLaneThreads, a, stream);
-}
-
-hipError_t launch_crc32c_blocks(int mode, const BlockArgs& a, hipStream_t stream,
-                                const char** name) {
+// one launch over a batch of at most FORST_ROWS_MAX_DESCS descriptors
+hipError_t launch_crc32c_slice(int mode, const BlockArgs& a, hipStream_t stream,
+                               const char** name) {
   const DeviceInfo& di = device_info();
-  if (a.n == 0) return hipSuccess;
   uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>((a.n + kWaves - 1) / kWaves, di.num_cus));
   if (grid == 0) grid = 1;
 #ifdef FORST_DEBUG_BOUNDS
@@ -1780,19 +1218,13 @@ hipError_t launch_crc32c_blocks(int mode, const BlockArgs& a, hipStream_t stream
     if (e != hipSuccess) return e;
   }
 #endif
-  // The rows kernel (one block per 16-lane row) for every block size.  In
-  // round 1 the v2 kernel (one block per wave, two 4 KiB steps in flight)
-  // won above 8-20 KiB; with the workgroup feed (stream_common.h) the rows
-  // kernel matches or beats it everywhere (profiles/ab_r02_late/
-  // rows_vs_v2_wgfeed.log, same box: 64 KiB 0.740 vs 0.736, the 4/16/64 KiB
-  // mix 0.726 vs 0.666, 512 K x 16 KiB 0.748 vs 0.705).  v2 remains for
-  // batches of 2^32 - 1 or more descriptors (the rows kernel indexes them
-  // with 32 bits).  Buffers shorter than one 4 KiB round take the simple
-  // kernel (the streaming kernels' dummy loads read [0, 4 KiB)).
-  CrcKernel k = a.base_len < kRB ? CrcKernel::kSimple
-                : (a.n < 0xffffffffull && (a.kernel_hint ? a.kernel_hint == 1 : true))
-                    ? CrcKernel::kRows
-                    : CrcKernel::kV2;
+  // The rows kernel (one block per 16-lane row) for every block size (a
+  // one-block-per-wave kernel with two 4 KiB steps in flight won above
+  // 8-20 KiB in round 1 and lost everywhere once the rows kernel had the
+  // workgroup feed: DESIGN.md 4.1b).  Buffers shorter than one 4 KiB round
+  // take the simple kernel (the streaming kernels' dummy loads read the
+  // buffer's first KiBs).
+  const CrcKernel k = a.base_len < kRB ? CrcKernel::kSimple : CrcKernel::kRows;
   // the WAL writer mode (wal_hs: header offsets + payload lengths, masked
   // output) exists in the rows kernel only
   if (a.wal_hs && (mode != kModeRaw || k != CrcKernel::kRows)) return hipErrorInvalidValue;
@@ -1810,6 +1242,26 @@ hipError_t launch_crc32c_blocks(int mode, const BlockArgs& a, hipStream_t stream
     default:
       return launch_crc_mode<kModeRaw>(k, a, grid, stream);
   }
+}
+
+}  // namespace
+
+// raw CRCs of messages all under kRawSplit bytes: the lane kernel alone (a
+// longer one would be left out: the caller guarantees the lengths)
+hipError_t launch_crc32c_raw_lanes(const BlockArgs& a, hipStream_t stream) {
+  if (a.n == 0) return hipSuccess;
+  return launch_kernel(crc32c_raw_lane_kernel, 2 * device_info().num_cus, kLaneThreads, a, stream);
+}
+
+hipError_t launch_crc32c_blocks(int mode, const BlockArgs& a, hipStream_t stream,
+                                const char** name) {
+  // (one launch unless the batch is longer than a rows launch can index)
+  for (uint64_t first = 0; first < a.n; first += FORST_ROWS_MAX_DESCS) {
+    const BlockArgs b = slice_descs(a, first, std::min<uint64_t>(a.n - first, FORST_ROWS_MAX_DESCS));
+    const hipError_t e = launch_crc32c_slice(mode, b, stream, name);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 }  // namespace forst

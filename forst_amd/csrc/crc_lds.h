@@ -1,14 +1,16 @@
-// forst_amd/csrc/crc_lds.h -- the LDS table machinery of the CRC32C kernels
-// (crc32c.hip) in the form the fused WAL-recovery kernel (xxh3.hip,
-// xxh3_frag_kernel<.., true>) uses: slicing tables replicated 8x so the 32
-// lanes of a ds_read_b32 bank group hit 32 distinct banks, each lookup
+// forst_amd/csrc/crc_lds.h -- the LDS table machinery of the CRC32C kernels:
+// the rows and lane kernels (crc32c.hip) and the fused WAL-recovery kernel
+// (xxh3.hip, xxh3_frag_kernel<.., true>).  Slicing tables replicated 8x so
+// the 32 lanes of a ds_read_b32 bank group hit 32 distinct banks, each lookup
 // address one v_perm_b32 of the data word and a per-lane constant.
 //
 // Layout [0, 64K): row e (byte value), dword d: d < 32 -> G_{d>>3}[e] copy
 // d & 7 (G = advance 4 bytes, the slicing-by-4 step), d >= 32 -> J_{..}[e]
-// (J = the chain's hop to its next chunk fused with the first dword step).
+// (J = the chain's hop to its next round or chunk fused with the first dword
+// step: each kernel fills in its own, kCrcJ3 or kCrcJ244).
 // Lane l (c = l & 7, g = (l >> 3) & 3) does lookup i on table i ^ g with byte
 // i ^ g of the word: address 256 * byte + 4 (8 (i ^ g) + c) [+ 128 for J].
+// Past the 64 KiB a kernel keeps unreplicated 4 x 256 shift tables (shift_at).
 #pragma once
 #include "device_common.h"
 
@@ -56,6 +58,37 @@ __device__ __forceinline__ uint32_t g_then(const uint8_t* __restrict__ Lb, const
   uint32_t l[4];
   look<false>(Lb, k, x, l);
   return xor3(l[0], l[1], xor3(l[2], l[3], e));
+}
+
+__device__ __forceinline__ uint32_t lane_c4(uint32_t lane) { return (lane & 7) << 2; }
+
+// replicated 4-table linear map: G (J = false) or the hop (J = true)
+template <bool J>
+__device__ __forceinline__ uint32_t rep_map(const uint8_t* __restrict__ Lb, const Lanes& k,
+                                            uint32_t x) {
+  uint32_t r = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    r ^= lds32(Lb, __builtin_amdgcn_perm(x, k.lpack, k.sel[i]) + (J ? 128u : 0u));
+  return r;
+}
+
+// k-byte slicing step (k <= 4, wave-uniform): the state after bytes y_0..y_k-1
+// (little-endian in y):  (s >> 8k) ^ XOR_j G[4-k+j][(s ^ y)_j]
+__device__ __forceinline__ uint32_t step_k(const uint8_t* __restrict__ Lb, const Lanes& kk,
+                                           uint32_t s, uint32_t y, uint32_t k) {
+  if (k == 0) return s;
+  const uint32_t x = s ^ y;
+  const uint32_t c4 = lane_c4(threadIdx.x);
+  uint32_t r = k == 4 ? 0u : (s >> (8 * k));
+#pragma unroll
+  for (uint32_t j = 0; j < 4; ++j) {
+    if (j < k) {
+      const uint32_t t = 4 - k + j;
+      r ^= lds32(Lb, __builtin_amdgcn_perm(x, c4, 0x0c0c0000u | ((4 + j) << 8)) + 32 * t);
+    }
+  }
+  return r;
 }
 
 // one 16-byte chunk after a gap: state' = G(J'(s) ^ w0 ...) with the hop

@@ -62,7 +62,9 @@ struct BlockArgs {
   // *ticket (zeroed per launch) or, without one, dealt round-robin
   unsigned long long* ticket;
   uint64_t share1;
-  int kernel_hint;  // CRC: 0 by mean block size, 1 rows kernel, 2 v2 kernel; XXH3: 3 v1 kernel
+  // XXH3 only: one message per wave (xxh3_stream_kernel) instead of one per
+  // 16-lane row -- a short list of long messages (wal_hash.h's gathered records)
+  bool xxh3_wave_per_message;
   // fused WAL-recovery CRC (launch_xxh3_frag_crc): per physical record, the
   // constants (E | Z << 32) and the CRC verdict; modifiers = the record's
   // first physical record index
@@ -83,6 +85,33 @@ struct BlockArgs {
   // launcher)
   uint32_t wg_cost;
 };
+
+// The rows kernels index a launch's descriptors with 32 bits (0xffffffff
+// means "none"): launch_crc32c_blocks and launch_xxh3_blocks split a longer
+// batch into launches of at most this many.  (A build option only so that a
+// test can run the split at a small n.)
+#ifndef FORST_ROWS_MAX_DESCS
+#define FORST_ROWS_MAX_DESCS 0x80000000ull
+#endif
+
+// a restricted to descriptors [first, first + count): the per-descriptor
+// arrays advanced, everything else (the buffer, the mismatches sum, ...) kept
+inline BlockArgs slice_descs(const BlockArgs& a, uint64_t first, uint64_t count) {
+  BlockArgs b = a;
+  const auto at = [first](auto* p) { return p ? p + first : p; };
+  b.offsets = at(a.offsets);
+  b.sizes = at(a.sizes);
+  b.last_bytes = at(a.last_bytes);
+  b.modifiers = at(a.modifiers);
+  b.init_crcs = at(a.init_crcs);
+  b.expect = at(a.expect);
+  b.out32 = at(a.out32);
+  b.out64 = at(a.out64);
+  b.stored_out = at(a.stored_out);
+  b.ok_out = at(a.ok_out);
+  b.n = count;
+  return b;
+}
 
 struct WalArgs {
   const uint8_t* log;

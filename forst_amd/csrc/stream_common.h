@@ -324,4 +324,16 @@ __device__ __forceinline__ bool desc_in_range(const BlockArgs& a, const Desc& d)
   return d.off <= a.base_len && need <= a.base_len - d.off;
 }
 
+// (host) a global-feed launch of `waves` waves per workgroup with its ticket
+// counter: feed_setup, the launch, the counter's release
+inline hipError_t launch_fed(void (*k)(BlockArgs), uint32_t grid, uint32_t waves, BlockArgs b,
+                             hipStream_t s) {
+  hipError_t e = feed_setup(b, uint64_t(grid) * waves, s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k, dim3(grid), dim3(64 * waves), 0, s, b);
+  e = hipGetLastError();
+  const hipError_t f = scratch_free(b.ticket, s);
+  return e != hipSuccess ? e : f;
+}
+
 }  // namespace forst

@@ -14,7 +14,7 @@
 //   scan    one workgroup turns tile sums into tile prefixes (+ total)
 //   fill    re-walks and writes one CRC descriptor per record
 //           (offset = header + 6, length = hs + len - 6) at its global index
-//   crc     crc32c_rows / stream2 kernel in raw mode over the descriptors --
+//   crc     the CRC32C rows kernels in raw mode over the descriptors --
 //           the bulk of the bytes, at the block kernels' streaming rate
 //   status  one lane per block compares computed vs stored masked CRCs and
 //           reports the first failure exactly as the serial reader would
@@ -467,7 +467,6 @@ hipError_t launch_wal_record_crc(const WalArgs& a, hipStream_t stream, const cha
     b.sizes = a.payload_lengths;
     b.out32 = crc;
     b.n = n;
-    b.kernel_hint = 1;  // the rows kernel (its WAL writer mode)
     b.wal_hs = a.recyclable ? kLogRHdr : kLogHdr;
     hipError_t e = launch_crc32c_blocks(kModeRaw, b, stream, name);
     if (e == hipSuccess && a.write_in_place) {

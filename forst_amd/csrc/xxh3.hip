@@ -2048,12 +2048,7 @@ hipError_t launch_xxh3_mode(XxKernel k, const BlockArgs& a, hipStream_t s, const
         b.wg_cost = FORST_XX_BLOCK_COST;
         return launch_kernel(xxh3_rows_kernel<M>, grid, b, s, kRowsThreads);
       }
-      BlockArgs b = a;
-      hipError_t e = feed_setup(b, uint64_t(grid) * kRowsWaves, s);
-      if (e != hipSuccess) return e;
-      e = launch_kernel(xxh3_rows_kernel<M>, grid, b, s, kRowsThreads);
-      const hipError_t f = scratch_free(b.ticket, s);
-      return e != hipSuccess ? e : f;
+      return launch_fed(xxh3_rows_kernel<M>, grid, kRowsWaves, a, s);
     }
     case XxKernel::kV1: {
       *name = kNames[2][M];
@@ -2088,15 +2083,8 @@ hipError_t launch_frag(const BlockArgs& a, hipStream_t stream, const char** name
   const uint32_t grid = static_cast<uint32_t>(std::max<uint64_t>(
       1, std::min<uint64_t>((a.n + 4 * FW - 1) / (4 * FW),
                             uint64_t(di.num_cus) * frag_occupancy<WPE, CRC, DEPTH>())));
-  BlockArgs b = a;
-  hipError_t e = feed_setup(b, uint64_t(grid) * FW, stream);
-  if (e != hipSuccess) return e;
   *name = CRC ? (WPE == 3 ? "xxh3_frag_kernel<3, crc>" : "xxh3_frag_kernel<2, crc>") : WPE == 4 ? "xxh3_frag_kernel<4>" : WPE == 3 ? "xxh3_frag_kernel<3>" : "xxh3_frag_kernel<2>";
-  hipLaunchKernelGGL((xxh3_frag_kernel<WPE, CRC, DEPTH>), dim3(grid),
-                     dim3(CRC ? kFragCrcThreads : kFragThreads), 0, stream, b);
-  e = hipGetLastError();
-  const hipError_t f = scratch_free(b.ticket, stream);
-  return e != hipSuccess ? e : f;
+  return launch_fed(xxh3_frag_kernel<WPE, CRC, DEPTH>, grid, FW, a, stream);
 }
 
 hipError_t launch_xxh3_frag(const BlockArgs& a, hipStream_t stream, const char** name) {
@@ -2153,22 +2141,19 @@ hipError_t launch_wal_short_rows(const uint8_t* base, uint64_t base_len, const u
   return hipGetLastError();
 }
 
-hipError_t launch_xxh3_blocks(int mode, const BlockArgs& a, hipStream_t stream,
-                              const char** name) {
-  if (a.n == 0) return hipSuccess;
-  // the rows kernel for every block size (it indexes descriptors with 32
-  // bits).  Round 1 sent uniform >= 48 KiB blocks to v1 (X64 rows 0.49 vs v1
-  // 0.62); with the workgroup feed rows win there too (X64 0.759 vs 0.644,
-  // profiles/ab_r02_late/xxh3_rows_vs_v1_wgfeed.log).  Buffers shorter than
-  // 4 KiB take the simple kernel (the streaming kernels' dummy loads read
-  // [0, 4 KiB)).
-  XxKernel k = a.base_len < 4096           ? XxKernel::kSimple
-               : a.n >= 0xffffffffull ? XxKernel::kV1
-                                           : XxKernel::kRows;
-  // kernel_hint 3: one message per wave (a short list of long messages, e.g.
+namespace {
+// one launch over a batch of at most FORST_ROWS_MAX_DESCS descriptors
+hipError_t launch_xxh3_slice(int mode, const BlockArgs& a, hipStream_t stream, const char** name) {
+  // the rows kernel for every block size.  Round 1 sent uniform >= 48 KiB
+  // blocks to v1 (X64 rows 0.49 vs v1 0.62); with the workgroup feed rows win
+  // there too (X64 0.759 vs 0.644, profiles/ab_r02_late/
+  // xxh3_rows_vs_v1_wgfeed.log).  Buffers shorter than 4 KiB take the simple
+  // kernel (the streaming kernels' dummy loads read [0, 4 KiB)).
+  XxKernel k = a.base_len < 4096 ? XxKernel::kSimple : XxKernel::kRows;
+  // one message per wave on request (a short list of long messages, e.g.
   // wal_hash.h's gathered records: rows would leave most rows idle while a
   // few walk 32 KiB records 1 KiB per step)
-  if (a.kernel_hint == 3 && a.base_len >= 4096) k = XxKernel::kV1;
+  if (a.xxh3_wave_per_message && a.base_len >= 4096) k = XxKernel::kV1;
   switch (mode) {
     case kModeCompute:
       return launch_xxh3_mode<kModeCompute>(k, a, stream, name);
@@ -2179,6 +2164,18 @@ hipError_t launch_xxh3_blocks(int mode, const BlockArgs& a, hipStream_t stream,
     default:
       return launch_xxh3_mode<kModeRaw>(k, a, stream, name);
   }
+}
+}  // namespace
+
+hipError_t launch_xxh3_blocks(int mode, const BlockArgs& a, hipStream_t stream,
+                              const char** name) {
+  // (one launch unless the batch is longer than a rows launch can index)
+  for (uint64_t first = 0; first < a.n; first += FORST_ROWS_MAX_DESCS) {
+    const BlockArgs b = slice_descs(a, first, std::min<uint64_t>(a.n - first, FORST_ROWS_MAX_DESCS));
+    const hipError_t e = launch_xxh3_slice(mode, b, stream, name);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 hipError_t launch_noop_blocks(int mode, const BlockArgs& a, hipStream_t stream,

@@ -46,14 +46,14 @@ SENTINEL8 = 0xA5
 # ---- dispatch rules ---------------------------------------------------------
 
 def crc_grid(n, num_cus):
-    """crc32c.hip launch_crc32c_blocks:
+    """crc32c.hip launch_crc32c_slice (per launch of launch_crc32c_blocks):
     grid = min((a.n + kWaves - 1) / kWaves, di.num_cus); if (grid == 0) grid = 1;"""
     return max(1, min((n + CRC_WAVES - 1) // CRC_WAVES, num_cus))
 
 
 def crc_raw_kernel(n, base_len, num_cus):
-    """crc32c.hip launch_crc32c_blocks / launch_crc_mode<kModeRaw>:
-    k = a.base_len < kRB ? kSimple : kRows;
+    """crc32c.hip launch_crc32c_slice / launch_crc_mode<kModeRaw>:
+    k = a.base_len < kRB ? CrcKernel::kSimple : CrcKernel::kRows;
     if (a.n < uint64_t(64) * grid * kWaves) crc32c_rows_raw_small_kernel
     else crc32c_raw_lane_kernel + launch_fed(crc32c_rows_raw_filt_kernel)"""
     if base_len < SIMPLE_BELOW:

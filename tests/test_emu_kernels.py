@@ -248,8 +248,9 @@ def test_emu_crc_stream_batches_and_edges():
 
 def test_emu_blocks_at_buffer_start():
     """Blocks whose first 32-byte lane segment would start in front of the
-    buffer (offset < 28, head dword index > offset/4): the v2 CRC kernel loads
-    that segment from offset 0 and re-aligns it in registers."""
+    buffer (offset < 28, head dword index > offset/4): the CRC rows kernel
+    loads that segment from offset 0 and re-aligns it in registers (q dwords,
+    crc32c.hip crow_derive / the head step)."""
     rng = np.random.default_rng(33)
     base = rng.integers(0, 256, 200000, dtype=np.uint8)
     offs, sizes = [], []
@@ -689,3 +690,128 @@ def test_emu_crc_trailer_direct_stores_of_tiny_blocks():
         exp[end + 1 + k] = (want >> np.uint32(8 * k)).astype(np.uint8)
     bad = np.nonzero(img != exp)[0]
     assert bad.size == 0, (bad.size, bad[:8].tolist())
+
+
+def test_emu_oversized_batches_are_split():
+    """A batch of more descriptors than one rows-kernel launch indexes
+    (engine.h FORST_ROWS_MAX_DESCS, 2^31; 1000 in this build) runs as several
+    launches over slices of the per-descriptor arrays: one launch (n = 1000),
+    a second slice of one descriptor (1001), two full slices (2000), three
+    with a ragged last one (2600).  The layout of
+    test_emu_crc_stream_batches_and_edges; CRC32C and XXH3 in every mode, raw
+    CRC32C with per-message init, raw XXH3, and the WAL writer's lengths mode
+    on more records than the limit.  Every result array starts as a sentinel
+    and is longer than the batch, so a slice stored at the wrong index shows."""
+    rng = np.random.default_rng(23)
+    nmax, pad = 2600, 8
+    sizes = rng.integers(0, 700, nmax).astype(np.uint32)
+    sizes[:40] = np.arange(40) + 40
+    sizes[40:48] = [4091, 4092, 4093, 4094, 4095, 4096, 8191, 12000]
+    sizes[[999, 1000, 1999, 2599]] = [333, 70, 4097, 150]  # (the blocks corrupted below)
+    offs = np.zeros(nmax, np.uint64)
+    offs[1:] = np.cumsum(sizes[:-1].astype(np.uint64) + 5 + rng.integers(0, 4, nmax - 1))
+    total = int(offs[-1]) + int(sizes[-1]) + 5 + 4096
+    base = emu._aligned(rng.integers(0, 256, total, dtype=np.uint8))
+    types = rng.integers(0, 8, nmax, dtype=np.uint8)
+    mods = rng.integers(0, 2**32, nmax, dtype=np.uint64).astype(np.uint32)
+    init = rng.integers(0, 2**32, nmax, dtype=np.uint64).astype(np.uint32)
+    # the references once, for the longest batch: the shorter ones are prefixes
+    want_mem = {t: O.block_checksum_batch(t, base, offs, sizes, modifiers=mods) for t in (1, 4)}
+    want_last = {t: O.block_checksum_batch(t, base, offs, sizes, last_bytes=types, modifiers=mods)
+                 for t in (1, 4)}
+    want_crc = np.array([O.crc32c_extend(int(i), base[int(o):int(o) + int(s)])
+                         for i, o, s in zip(init, offs, sizes)], np.uint32)
+    want_xxh = O.xxh3_batch(base, offs, sizes)
+    S32, S64, S8 = 0xA5A5A5A5, 0xA5A5A5A5A5A5A5A5, 0xA5
+    p = emu._p
+
+    def filled(n, dtype, v):
+        return np.full(n + pad, v, dtype)
+
+    import ctypes
+    import dispatch
+    cus = int(os.environ.get("FORST_EMU_CUS", 2))  # (tests/emu/hip/hip_runtime.h)
+    with emu.variant("-DFORST_ROWS_MAX_DESCS=1000"):
+        L = emu.lib()
+        L.forst_last_kernel.restype = ctypes.c_char_p
+        for n in (1000, 1001, 2000, 2600):
+            o, s, ty, md = offs[:n].copy(), sizes[:n].copy(), types[:n].copy(), mods[:n].copy()
+            ini = init[:n].copy()
+            for t in (1, 4):
+                # compute: the type byte from last_bytes[] and from memory
+                for last, want in ((ty, want_last[t]), (None, want_mem[t])):
+                    out = filled(n, np.uint32, S32)
+                    emu._chk(L.forst_block_checksum_batch(t, p(base), base.nbytes, p(o), p(s),
+                                                          p(last), p(md), p(out), n, None))
+                    assert (out[:n] == want[:n]).all() and (out[n:] == S32).all(), (t, n)
+                # trailer: values and the image
+                img = emu._aligned(base)
+                out = filled(n, np.uint32, S32)
+                emu._chk(L.forst_block_trailer_batch(t, p(img), img.nbytes, p(o), p(s), p(ty),
+                                                     p(md), p(out), n, None))
+                assert (out[:n] == want_last[t][:n]).all() and (out[n:] == S32).all(), (t, n)
+                exp = base.copy()
+                end = (o + s).astype(np.int64)
+                exp[end] = ty
+                for k in range(4):
+                    exp[end + 1 + k] = (want_last[t][:n] >> np.uint32(8 * k)).astype(np.uint8)
+                assert (img == exp).all(), (t, n)
+                # verify: a corrupted block in the first slice and one in the
+                # last, an out-of-range descriptor in a later slice (n = 1000
+                # and 1001 have no later slice with room for it)
+                hit = [7, n - 1]
+                oor = 1500 if n > 1500 else n // 2
+                for k in hit:
+                    img[int(o[k]) + 3] ^= 0x10
+                ov = o.copy()
+                ov[oor] = total + 100
+                comp, st = filled(n, np.uint32, S32), filled(n, np.uint32, S32)
+                ok = filled(n, np.uint8, S8)
+                bad = np.zeros(1, np.uint64)
+                emu._chk(L.forst_block_verify_batch(t, p(img), img.nbytes, p(ov), p(s), p(md),
+                                                    p(comp), p(st), p(ok), p(bad), n, None))
+                # computed = the checksum of the bytes as they are, without the
+                # modifier; stored = the trailer's value without it
+                ecomp = O.block_checksum_batch(t, img, o, s, modifiers=md) - md
+                est = want_last[t][:n] - md
+                eok = np.ones(n, np.uint8)
+                eok[hit] = 0
+                ecomp[oor], est[oor], eok[oor] = 0, 0, 0
+                assert (ecomp[hit] != est[hit]).all()
+                assert int(bad[0]) == 3, (t, n, int(bad[0]))
+                assert (ok[:n] == eok).all() and (ok[n:] == S8).all(), (t, n)
+                assert (st[:n] == est).all() and (st[n:] == S32).all(), (t, n)
+                assert (comp[:n] == ecomp).all() and (comp[n:] == S32).all(), (t, n)
+            # raw CRC32C with per-message init, raw XXH3
+            out = filled(n, np.uint32, S32)
+            emu._chk(L.forst_crc32c_batch(p(base), base.nbytes, p(o), p(s), p(ini), p(out),
+                                          n, None))
+            assert (out[:n] == want_crc[:n]).all() and (out[n:] == S32).all(), n
+            # the last launch was the last slice's: at n = 2600 its 600
+            # descriptors take the small-batch kernel, 2600 in one launch on the
+            # emulator's 2 workgroups would not (dispatch.crc_raw_kernel)
+            last_n = n - (n - 1) // 1000 * 1000
+            assert L.forst_last_kernel() == dispatch.crc_raw_kernel(last_n, base.nbytes, cus).encode()
+            out = filled(n, np.uint64, S64)
+            emu._chk(L.forst_xxh3_64_batch(p(base), base.nbytes, p(o), p(s), p(out), n, None))
+            assert (out[:n] == want_xxh[:n]).all() and (out[n:] == S64).all(), n
+        # the WAL writer's lengths mode (raw CRC rows kernel, wal_hs) on a
+        # record list longer than the limit: every header CRC, in place and
+        # in the array
+        lens = rng.integers(0, 600, 2300).astype(np.uint32)
+        payload = rng.integers(0, 256, int(lens.astype(np.int64).sum()), dtype=np.uint8)
+        buf, poffs, plens = O.wal_frame(payload, lens, log_number=3)
+        nrec = len(poffs)
+        assert nrec > 2000
+        w = emu._aligned(buf)
+        for q in poffs:
+            w[int(q):int(q) + 4] = 0
+        po = np.ascontiguousarray(poffs, np.uint64)
+        pl = np.ascontiguousarray(plens, np.uint32)
+        crcs = filled(nrec, np.uint32, S32)
+        emu._chk(L.forst_wal_record_crc_lengths(p(w), w.nbytes, p(po), p(pl), nrec, 0, 1, p(crcs),
+                                                None))
+        assert (w[:len(buf)] == buf).all()
+        assert (crcs[:nrec] == np.frombuffer(b"".join(buf[int(q):int(q) + 4].tobytes()
+                                                      for q in poffs), np.uint32)).all()
+        assert (crcs[nrec:] == S32).all()
