@@ -65,6 +65,7 @@ def lib():
         "forst_block_verify_batch": (i, [i, vp, u64, vp, vp, vp, vp, vp, vp, vp, u64, vp]),
         "forst_crc32c_batch": (i, [vp, u64, vp, vp, vp, vp, u64, vp]),
         "forst_crc32c_buffer": (i, [vp, u64, u32, vp, vp]),
+        "forst_crc32c_files": (i, [vp, u64, vp, vp, vp, vp, u64, vp]),
         "forst_wal_record_xxh3_batch": (i, [vp, u64, vp, u64, vp, vp, vp, vp]),
         "forst_sst_footer_decode": (i, [vp, u64, u64, vp]),
         "forst_sst_index_handles": (i, [vp, u64, i, i, vp, vp, u64, vp]),
@@ -107,6 +108,9 @@ def lib():
         "forst_trailer_writer_add": (i, [vp, vp, u64, ctypes.c_uint8, i, vp, vp]),
         "forst_trailer_writer_flush": (i, [vp]),
         "forst_trailer_writer_footer": (i, [vp, u32, u64, u64, u64, u64]),
+        "forst_trailer_writer_enable_file_checksum": (i, [vp, u32]),
+        "forst_trailer_writer_set_crc_sink": (i, [vp, vp, vp]),
+        "forst_trailer_writer_file_checksum": (i, [vp, vp, vp]),
         "forst_trailer_writer_offset": (u64, [vp]),
         "forst_trailer_writer_close": (i, [vp]),
         "forst_trailer_writer_last_error": (ctypes.c_char_p, []),

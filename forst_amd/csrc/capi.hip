@@ -413,6 +413,30 @@ FORST_API int forst_crc32c_buffer(const uint8_t* base, uint64_t len, uint32_t in
                     "crc32c_buffer launch");
 }
 
+FORST_API int forst_crc32c_files(const uint8_t* arena, uint64_t arena_len, const uint64_t* offsets,
+                                 const uint64_t* lengths, const uint32_t* inits, uint32_t* out,
+                                 uint64_t n_files, void* stream) {
+  if (n_files == 0) return FORST_OK;
+  if (!offsets || !lengths || !out)
+    return set_error(FORST_EINVAL, "offsets/lengths/out must be non-null");
+  if (n_files > (uint64_t(1) << 40)) return set_error(FORST_EINVAL, "n_files too large");
+  bool any = false;
+  for (uint64_t f = 0; f < n_files; ++f) {
+    if (offsets[f] > arena_len || lengths[f] > arena_len - offsets[f])
+      return set_error(FORST_EINVAL, "file " + std::to_string(f) + " [" +
+                                         std::to_string(offsets[f]) + ", +" +
+                                         std::to_string(lengths[f]) + ") outside the arena of " +
+                                         std::to_string(arena_len) + " bytes");
+    any |= lengths[f] != 0;
+  }
+  if (any && !arena) return set_error(FORST_EINVAL, "arena must be non-null");
+  int rc = check_device();
+  if (rc) return rc;
+  return hip_status(launch_crc32c_files(arena, arena_len, offsets, lengths, inits, out, n_files,
+                                        static_cast<hipStream_t>(stream), &g_last_kernel),
+                    "crc32c_files launch");
+}
+
 FORST_API int forst_crc32c_combine_batch(const uint32_t* crc1, const uint32_t* crc2,
                                          const uint64_t* len2, uint32_t* out, uint64_t n,
                                          void* stream) {

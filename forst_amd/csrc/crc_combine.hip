@@ -17,6 +17,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstring>
+#include <vector>
 
 #include "../../include/forst_checksum.h"
 #include "crc32c_tables.h"
@@ -94,6 +96,67 @@ __global__ void __launch_bounds__(kCombThreads)
   if ((threadIdx.x & 63) == 0 && v) atomicXor(out, v);
 }
 
+// ---- whole-file CRC32C over a set of buffers (forst_crc32c_files) ------------
+// Every file is cut into 64 KiB chunks under ONE global chunk index; pre[f] =
+// chunks before file f (pre[n] = all of them), built on the host.  A chunk's
+// file is the last f with pre[f] <= chunk (files without chunks share their
+// successor's entry and are never found: their result is the init term alone).
+__device__ inline uint64_t file_of_chunk(const uint64_t* pre, uint64_t n_files, uint64_t c) {
+  uint64_t lo = 0, hi = n_files;  // pre[lo] <= c < pre[hi]
+  while (hi - lo > 1) {
+    const uint64_t mid = lo + (hi - lo) / 2;
+    if (pre[mid] <= c) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// chunk c -> (offset from the 4-byte aligned base, size); file f -> its
+// init term M(length) * init, stored (not XORed), so `out` needs no memset and
+// a stale value never survives.  One thread per max(chunks, files).
+__global__ void __launch_bounds__(kCombThreads)
+    files_desc_kernel(const uint64_t* pre, const uint64_t* foffs, const uint64_t* flens,
+                      const uint32_t* inits, uint64_t n_files, uint64_t n_chunks, uint64_t delta,
+                      uint64_t* offs, uint32_t* sizes, uint32_t* out) {
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kCombThreads + threadIdx.x;
+  if (i < n_files) out[i] = inits ? gf_mul(x8n_dev(flens[i]), inits[i]) : 0u;
+  if (i >= n_chunks) return;
+  const uint64_t f = file_of_chunk(pre, n_files, i);
+  const uint64_t at = (i - pre[f]) * kChunk, left = flens[f] - at;
+  offs[i] = delta + foffs[f] + at;
+  sizes[i] = static_cast<uint32_t>(left < kChunk ? left : kChunk);
+}
+
+// One lane per chunk: its CRC shifted to the end of its own file, lanes of the
+// same file XOR-reduced inside the wave (a segmented reduction: files are runs
+// of consecutive lanes), one atomicXor per (wave, file) from the run's first
+// lane.  A wave inside one long file issues one atomic; a wave of 64
+// one-chunk files issues 64.
+__global__ void __launch_bounds__(kCombThreads)
+    files_fold_kernel(const uint32_t* crcs, const uint64_t* pre, const uint64_t* flens,
+                      uint64_t n_files, uint64_t n_chunks, uint32_t* out) {
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kCombThreads + threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63;
+  uint64_t f = ~uint64_t(0);  // lanes past the last chunk: a run of their own
+  uint32_t v = 0;
+  if (i < n_chunks) {
+    f = file_of_chunk(pre, n_files, i);
+    const uint64_t end = (i - pre[f] + 1) * kChunk, len = flens[f];
+    v = gf_mul(x8n_dev(end < len ? len - end : 0), crcs[i]);
+  }
+  const uint32_t flo = static_cast<uint32_t>(f), fhi = static_cast<uint32_t>(f >> 32);
+  // every lane takes part in every shuffle (no early exit above)
+  const int prev = lane ? static_cast<int>(lane) - 1 : 0;
+  const uint32_t plo = __shfl(flo, prev), phi = __shfl(fhi, prev);
+  const bool head = lane == 0 || plo != flo || phi != fhi;
+  for (uint32_t d = 1; d < 64; d <<= 1) {
+    const int src = static_cast<int>(lane + d < 64 ? lane + d : 63);
+    const uint32_t ov = __shfl(v, src), olo = __shfl(flo, src), ohi = __shfl(fhi, src);
+    // after this step v covers lanes [lane, lane + 2d) of this lane's run
+    if (lane + d < 64 && olo == flo && ohi == fhi) v ^= ov;
+  }
+  if (head && i < n_chunks && v) atomicXor(out + f, v);
+}
+
 }  // namespace
 
 hipError_t launch_crc32c_combine_batch(const uint32_t* crc1, const uint32_t* crc2,
@@ -136,6 +199,65 @@ hipError_t launch_crc32c_buffer(const uint8_t* base, uint64_t len, uint32_t init
   hipLaunchKernelGGL(chunk_fold_kernel, grid, dim3(kCombThreads), 0, stream, crcs, len, nc, init,
                      out);
   if (e == hipSuccess) e = hipGetLastError();
+  const hipError_t f = scratch_free(scratch, stream);
+  return e != hipSuccess ? e : f;
+}
+
+hipError_t launch_crc32c_files(const uint8_t* arena, uint64_t arena_len, const uint64_t* offsets,
+                               const uint64_t* lengths, const uint32_t* inits, uint32_t* out,
+                               uint64_t n_files, hipStream_t stream, const char** name) {
+  if (n_files == 0) return hipSuccess;
+  // host block [pre (n + 1) | offsets n | lengths n | inits n], one upload
+  const uint64_t words = 3 * n_files + 1;
+  std::vector<uint64_t> host(words + (inits ? (n_files + 1) / 2 : 0));
+  uint64_t* pre = host.data();
+  pre[0] = 0;
+  for (uint64_t f = 0; f < n_files; ++f) pre[f + 1] = pre[f] + (lengths[f] + kChunk - 1) / kChunk;
+  std::memcpy(pre + n_files + 1, offsets, 8 * n_files);
+  std::memcpy(pre + 2 * n_files + 1, lengths, 8 * n_files);
+  if (inits) std::memcpy(pre + words, inits, 4 * n_files);
+  const uint64_t nc = pre[n_files];
+  const size_t sh = (8 * host.size() + 255) & ~size_t(255);
+  const size_t so = (8 * nc + 255) & ~size_t(255), ss = (4 * nc + 255) & ~size_t(255);
+  void* scratch = nullptr;
+  hipError_t e = scratch_alloc(&scratch, sh + so + 2 * ss, stream);
+  if (e != hipSuccess) return e;
+  uint8_t* sc = static_cast<uint8_t*>(scratch);
+  const uint64_t* d_pre = reinterpret_cast<const uint64_t*>(sc);
+  const uint64_t* d_foffs = d_pre + n_files + 1;
+  const uint64_t* d_flens = d_foffs + n_files;
+  const uint32_t* d_inits = inits ? reinterpret_cast<const uint32_t*>(d_pre + words) : nullptr;
+  uint64_t* offs = reinterpret_cast<uint64_t*>(sc + sh);
+  uint32_t* sizes = reinterpret_cast<uint32_t*>(sc + sh + so);
+  uint32_t* crcs = reinterpret_cast<uint32_t*>(sc + sh + so + ss);
+  // (pageable source: the copy has left `host` when hipMemcpyAsync returns)
+  e = hipMemcpyAsync(scratch, host.data(), 8 * host.size(), hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess) {
+    // the block kernels want a 4-byte aligned base: step back to one, the
+    // chunk offsets carry the difference
+    const uint64_t delta = reinterpret_cast<uintptr_t>(arena) & 3;
+    const uint64_t nt = nc > n_files ? nc : n_files;
+    *name = "files_desc_kernel";
+    hipLaunchKernelGGL(files_desc_kernel, dim3(static_cast<uint32_t>((nt + kCombThreads - 1) / kCombThreads)),
+                       dim3(kCombThreads), 0, stream, d_pre, d_foffs, d_flens, d_inits, n_files, nc,
+                       delta, offs, sizes, out);
+    if (nc) {
+      BlockArgs b{};
+      b.base = arena - delta;
+      b.base_len = arena_len + delta;
+      b.offsets = offs;
+      b.sizes = sizes;
+      b.out32 = crcs;
+      b.n = nc;
+      e = launch_crc32c_blocks(kModeRaw, b, stream, name);
+      if (e == hipSuccess) {
+        *name = "files_fold_kernel";
+        hipLaunchKernelGGL(files_fold_kernel, dim3(static_cast<uint32_t>((nc + kCombThreads - 1) / kCombThreads)),
+                           dim3(kCombThreads), 0, stream, crcs, d_pre, d_flens, n_files, nc, out);
+      }
+    }
+    if (e == hipSuccess) e = hipGetLastError();
+  }
   const hipError_t f = scratch_free(scratch, stream);
   return e != hipSuccess ? e : f;
 }

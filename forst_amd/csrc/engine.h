@@ -344,6 +344,11 @@ hipError_t launch_crc32c_combine_batch(const uint32_t* crc1, const uint32_t* crc
                                        hipStream_t stream, const char** kernel_name);
 hipError_t launch_crc32c_buffer(const uint8_t* base, uint64_t len, uint32_t init, uint32_t* out,
                                 hipStream_t stream, const char** kernel_name);
+// out[f] = Extend(inits ? inits[f] : 0, arena + offsets[f], lengths[f]) for
+// HOST offsets / lengths / inits (ranges checked by the caller)
+hipError_t launch_crc32c_files(const uint8_t* arena, uint64_t arena_len, const uint64_t* offsets,
+                               const uint64_t* lengths, const uint32_t* inits, uint32_t* out,
+                               uint64_t n_files, hipStream_t stream, const char** kernel_name);
 hipError_t launch_wal_record_xxh3(const WalArgs& a, uint64_t* out, uint64_t* out_first,
                                   uint64_t* n_logical_host, hipStream_t stream,
                                   const char** kernel_name);

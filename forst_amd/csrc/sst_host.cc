@@ -725,6 +725,98 @@ std::vector<Status> VerifySstFilesChecksums(BlockChecksumEngine& eng,
   return out;
 }
 
+// ---- whole-file checksums (DB::VerifyFileChecksums) --------------------------
+
+// FileChecksumGenCrc32c::Finalize (util/file_checksum_helper.h:35-41):
+// PutFixed32(EndianSwapValue(crc)), the 4 bytes big-endian
+std::string FileChecksumToString(uint32_t crc) {
+  std::string s(4, '\0');
+  for (int i = 0; i < 4; ++i) s[i] = static_cast<char>(crc >> (24 - 8 * i));
+  return s;
+}
+
+bool FileChecksumFromString(const std::string& s, uint32_t* crc) {
+  if (s.size() != 4) return false;
+  uint32_t c = 0;
+  for (int i = 0; i < 4; ++i) c = (c << 8) | static_cast<uint8_t>(s[i]);
+  if (crc) *crc = c;
+  return true;
+}
+
+// Slice::ToString(true) (util/slice.cc): two upper-case hex digits per byte
+std::string FileChecksumHex(const std::string& s) {
+  static const char kHex[] = "0123456789ABCDEF";
+  std::string h;
+  h.reserve(2 * s.size());
+  for (unsigned char c : s) {
+    h.push_back(kHex[c >> 4]);
+    h.push_back(kHex[c & 15]);
+  }
+  return h;
+}
+
+std::vector<uint32_t> FileChecksums(BlockChecksumEngine& eng, const std::vector<SstFileRef>& files,
+                                    const uint8_t* dev_arena, uint64_t arena_len, Status* status) {
+  const uint64_t n = files.size();
+  std::vector<uint32_t> out(n, 0);
+  Status s;
+  if (n) {
+    hipStream_t st = static_cast<hipStream_t>(eng.stream());
+    std::vector<uint64_t> offs(n), lens(n);
+    for (uint64_t i = 0; i < n; ++i) {
+      offs[i] = files[i].dev_offset;
+      lens[i] = files[i].file_size;
+    }
+    void* d = nullptr;
+    s = hip_status(hipMallocAsync(&d, n * 4, st), "hipMallocAsync");
+    if (s.ok()) {
+      const int rc = forst_crc32c_files(dev_arena, arena_len, offs.data(), lens.data(), nullptr,
+                                        static_cast<uint32_t*>(d), n, eng.stream());
+      if (rc == FORST_EINVAL) s = Status::InvalidArgument(forst_last_error());
+      else if (rc) s = Status::IOError(std::string("crc32c_files: ") + forst_last_error());
+      if (s.ok()) s = hip_status(hipMemcpyAsync(out.data(), d, n * 4, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+      if (s.ok()) s = hip_status(hipStreamSynchronize(st), "hipStreamSynchronize");
+      (void)hipFreeAsync(d, st);
+    }
+  }
+  if (status) *status = s;
+  return out;
+}
+
+// DBImpl::VerifyFullFileChecksum (db/db_impl/db_impl.cc:6373-6402) per file
+std::vector<Status> VerifyFullFileChecksums(BlockChecksumEngine& eng,
+                                            const std::vector<SstFileRef>& files,
+                                            const uint8_t* dev_arena, uint64_t arena_len,
+                                            const std::vector<std::string>& expected) {
+  const size_t n = files.size();
+  if (expected.size() != n)
+    return std::vector<Status>(n, Status::InvalidArgument("one expected checksum per file"));
+  // (files whose expected checksum is kUnknownFileChecksum are not read)
+  std::vector<SstFileRef> todo;
+  std::vector<size_t> which;
+  for (size_t i = 0; i < n; ++i)
+    if (!expected[i].empty()) {
+      todo.push_back(files[i]);
+      which.push_back(i);
+    }
+  std::vector<Status> out(n);
+  Status s;
+  const std::vector<uint32_t> crcs = FileChecksums(eng, todo, dev_arena, arena_len, &s);
+  for (size_t k = 0; k < which.size(); ++k) {
+    const size_t i = which[k];
+    if (!s.ok()) {
+      out[i] = s;
+      continue;
+    }
+    const std::string actual = FileChecksumToString(crcs[k]);
+    if (actual != expected[i])
+      out[i] = Status::Corruption(files[i].file_name + " file checksum mismatch, expecting " +
+                                  FileChecksumHex(expected[i]) + ", but actual " +
+                                  FileChecksumHex(actual));
+  }
+  return out;
+}
+
 }  // namespace forst_gpu
 
 namespace {

@@ -63,6 +63,15 @@ uint8_t* PutVarint64(uint8_t* p, uint64_t v) {  // util/coding.h
   *p++ = static_cast<uint8_t>(v);
   return p;
 }
+// crc32c::Value of a few bytes on the host (the footer: 48 or 53 bytes)
+uint32_t SmallCrc32c(const uint8_t* p, size_t n) {
+  uint32_t c = 0xffffffffu;
+  for (size_t i = 0; i < n; ++i) {
+    c ^= p[i];
+    for (int k = 0; k < 8; ++k) c = (c >> 1) ^ ((c & 1u) ? 0x82f63b78u : 0u);
+  }
+  return ~c;
+}
 }  // namespace
 
 struct GpuTrailerWriter::Window {
@@ -73,6 +82,8 @@ struct GpuTrailerWriter::Window {
   uint8_t* d = nullptr;    // device copy
   std::vector<uint64_t> offs;  // block offsets in the window
   std::vector<uint32_t> sizes, mods;
+  std::vector<uint8_t> lasts;  // compression types (file checksum / CRC sink only)
+  uint8_t* d_lasts = nullptr;
   uint64_t dcap_blocks = 0;
   uint64_t* d_offs = nullptr;
   uint32_t *d_sizes = nullptr, *d_mods = nullptr, *d_out = nullptr;
@@ -82,9 +93,45 @@ struct GpuTrailerWriter::Window {
 };
 
 GpuTrailerWriter::GpuTrailerWriter(const Options& opt, Sink sink, void* stream)
-    : opt_(opt), sink_(std::move(sink)), stream_(stream), offset_(opt.start_offset) {
+    : opt_(opt), sink_(std::move(sink)), file_crc_(opt.file_checksum_init), stream_(stream),
+      offset_(opt.start_offset) {
   win_[0] = new Window();
   win_[1] = new Window();
+}
+
+GpuTrailerWriter::GpuTrailerWriter(const Options& opt, SinkWithCrc sink, void* stream)
+    : opt_(opt), crc_sink_(std::move(sink)), file_crc_(opt.file_checksum_init), stream_(stream),
+      offset_(opt.start_offset) {
+  win_[0] = new Window();
+  win_[1] = new Window();
+}
+
+Status GpuTrailerWriter::EnableFileChecksum(uint32_t init) {
+  if (offset_ != opt_.start_offset) return Status::InvalidArgument("blocks were already added");
+  opt_.file_checksum = true;
+  opt_.file_checksum_init = file_crc_ = init;
+  return Status::OK();
+}
+
+Status GpuTrailerWriter::SetCrcSink(SinkWithCrc sink) {
+  if (offset_ != opt_.start_offset) return Status::InvalidArgument("blocks were already added");
+  if (!sink) return Status::InvalidArgument("null sink");
+  crc_sink_ = std::move(sink);
+  return Status::OK();
+}
+
+std::string GpuTrailerWriter::FileChecksumString() const {
+  return FileChecksumToString(file_crc_);
+}
+
+// n final bytes on to the file; crc = crc32c::Value of them (used only when
+// the file checksum or the CRC sink is on)
+Status GpuTrailerWriter::Emit(const uint8_t* data, uint64_t n, uint32_t crc) {
+  Status s = crc_sink_ ? crc_sink_(reinterpret_cast<const char*>(data), n, crc)
+                       : sink_(reinterpret_cast<const char*>(data), n);
+  // Extend(running, data) = Combine(running, Value(data), n)
+  if (s.ok() && opt_.file_checksum) file_crc_ = forst_crc32c_combine(file_crc_, crc, n);
+  return s;
 }
 
 GpuTrailerWriter::~GpuTrailerWriter() {
@@ -126,13 +173,15 @@ Status GpuTrailerWriter::Reserve(Window& w, uint64_t bytes, uint64_t blocks) {
     w.h_out = nullptr;
     w.dcap_blocks = 0;
     void* p = nullptr;
-    Status s = HipS(hipMalloc(&p, nb * 20), "hipMalloc");
+    // (d_out and h_out: one more slot, the window's own CRC behind the blocks')
+    Status s = HipS(hipMalloc(&p, nb * 21 + 4), "hipMalloc");
     if (!s.ok()) return s;
     w.d_offs = static_cast<uint64_t*>(p);
     w.d_sizes = reinterpret_cast<uint32_t*>(w.d_offs + nb);
     w.d_mods = w.d_sizes + nb;
     w.d_out = w.d_mods + nb;
-    s = HipS(hipHostMalloc(&p, nb * 4), "hipHostMalloc");
+    w.d_lasts = reinterpret_cast<uint8_t*>(w.d_out + nb + 1);
+    s = HipS(hipHostMalloc(&p, (nb + 1) * 4), "hipHostMalloc");
     if (!s.ok()) return s;
     w.h_out = static_cast<uint32_t*>(p);
     w.dcap_blocks = nb;
@@ -153,10 +202,22 @@ Status GpuTrailerWriter::Launch(Window& w) {
   if (!s.ok()) return s;
   // ComputeBuiltinChecksumWithLastByte(type, block, n, comp_type) +
   // ChecksumModifierForContext(base, offset): the type byte is in the window
-  const int rc = forst_block_checksum_batch(opt_.checksum, w.d, w.len, w.d_offs, w.d_sizes, nullptr,
-                                            ctx ? w.d_mods : nullptr, w.d_out, n, stream_);
+  int rc;
+  if (!want_crc()) {
+    rc = forst_block_checksum_batch(opt_.checksum, w.d, w.len, w.d_offs, w.d_sizes, nullptr,
+                                    ctx ? w.d_mods : nullptr, w.d_out, n, stream_);
+  } else {
+    // the trailers written into the device copy too, then crc32c::Value of
+    // the window's final bytes from that copy: the window crosses the bus once
+    // and its CRC comes back with the block checksums
+    s = HipS(hipMemcpyAsync(w.d_lasts, w.lasts.data(), n, hipMemcpyHostToDevice, st), "hipMemcpyAsync");
+    if (!s.ok()) return s;
+    rc = forst_block_trailer_batch(opt_.checksum, w.d, w.len, w.d_offs, w.d_sizes, w.d_lasts,
+                                   ctx ? w.d_mods : nullptr, w.d_out, n, stream_);
+    if (rc == FORST_OK) rc = forst_crc32c_buffer(w.d, w.len, 0, w.d_out + n, stream_);
+  }
   if (rc != FORST_OK) return Status::IOError(std::string("trailer batch: ") + forst_last_error());
-  s = HipS(hipMemcpyAsync(w.h_out, w.d_out, n * 4, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+  s = HipS(hipMemcpyAsync(w.h_out, w.d_out, (n + (want_crc() ? 1 : 0)) * 4, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
   if (s.ok()) s = HipS(hipEventRecord(w.done, st), "hipEventRecord");
   if (s.ok()) {
     w.in_flight = true;
@@ -174,13 +235,14 @@ Status GpuTrailerWriter::Retire(Window& w) {
     w.in_flight = false;
   }
   if (w.len) {
-    Status s = sink_(reinterpret_cast<const char*>(w.h), w.len);
+    Status s = Emit(w.h, w.len, want_crc() ? w.h_out[w.offs.size()] : 0);
     if (!s.ok()) return s;
   }
   w.len = 0;
   w.offs.clear();
   w.sizes.clear();
   w.mods.clear();
+  w.lasts.clear();
   return Status::OK();
 }
 
@@ -215,13 +277,14 @@ Status GpuTrailerWriter::AddBlock(const char* data, size_t n, uint8_t compressio
   *handle_offset = offset_;
   *handle_size = n;
   uint8_t* p = w->h + w->len;
-  std::memcpy(p, data, n);
+  if (n) std::memcpy(p, data, n);  // (an empty block may come with a null pointer)
   p[n] = compression_type;  // trailer[0]; the LE32 checksum comes from the GPU
   std::memset(p + n + 1, 0, 4);
   if (pad) std::memset(p + n + kTrailer, 0, pad);  // WritableFileWriter::Pad
   w->offs.push_back(w->len);
   w->sizes.push_back(static_cast<uint32_t>(n));
   w->mods.push_back(ChecksumModifierForContext(opt_.base_context_checksum, offset_));
+  if (want_crc()) w->lasts.push_back(compression_type);
   w->len += need;
   offset_ += need;
   return Status::OK();
@@ -250,7 +313,7 @@ Status GpuTrailerWriter::WriteFooter(uint32_t format_version, uint64_t metaindex
                                         metaindex_size, index_offset, index_size, f, &len,
                                         stream_);
   if (rc != FORST_OK) return status_ = Status::InvalidArgument(forst_sst_last_error());
-  s = sink_(reinterpret_cast<const char*>(f), len);
+  s = Emit(f, len, want_crc() ? SmallCrc32c(f, len) : 0);
   if (s.ok()) offset_ += len;
   return s;
 }
@@ -329,6 +392,33 @@ FORST_API int forst_trailer_writer_footer(forst_trailer_writer* w, uint32_t form
   forst_gpu::Status s = w->w->WriteFooter(format_version, metaindex_offset, metaindex_size,
                                         index_offset, index_size);
   return s.ok() ? FORST_OK : tw_fail(s);
+}
+
+FORST_API int forst_trailer_writer_enable_file_checksum(forst_trailer_writer* w, uint32_t init) {
+  if (!w) return tw_fail(forst_gpu::Status::InvalidArgument("null writer"));
+  forst_gpu::Status s = w->w->EnableFileChecksum(init);
+  return s.ok() ? FORST_OK : tw_fail(s);
+}
+
+FORST_API int forst_trailer_writer_set_crc_sink(forst_trailer_writer* w, forst_sink_crc_fn sink,
+                                                void* sink_arg) {
+  if (!w || !sink) return tw_fail(forst_gpu::Status::InvalidArgument("null writer / sink"));
+  forst_gpu::Status s = w->w->SetCrcSink([sink, sink_arg](const char* d, size_t n, uint32_t crc) {
+    return sink(sink_arg, reinterpret_cast<const uint8_t*>(d), n, crc) == 0
+               ? forst_gpu::Status::OK()
+               : forst_gpu::Status::IOError("sink failed");
+  });
+  return s.ok() ? FORST_OK : tw_fail(s);
+}
+
+FORST_API int forst_trailer_writer_file_checksum(const forst_trailer_writer* w, uint32_t* crc,
+                                                 uint8_t be4[4]) {
+  if (!w) return tw_fail(forst_gpu::Status::InvalidArgument("null writer"));
+  const uint32_t c = w->w->file_checksum();
+  if (crc) *crc = c;
+  if (be4)
+    for (int i = 0; i < 4; ++i) be4[i] = static_cast<uint8_t>(c >> (24 - 8 * i));
+  return FORST_OK;
 }
 
 FORST_API uint64_t forst_trailer_writer_offset(const forst_trailer_writer* w) {

@@ -10,6 +10,7 @@ torch's current stream.
 import ctypes
 import enum
 
+import numpy as np
 import torch
 
 from ._lib import check, lib
@@ -139,6 +140,33 @@ def crc32c_buffer(base, init=0, out=None, stream=None):
     check(lib().forst_crc32c_buffer(base.data_ptr(), base.numel(), init & 0xFFFFFFFF,
                                     out.data_ptr(), _stream(stream)))
     return out
+
+
+def crc32c_files(arena, offsets, lengths, inits=None, out=None, stream=None):
+    """crc32c::Extend(inits[i] or 0, arena[offsets[i] : offsets[i] + lengths[i]])
+    for a set of files in one call (FileChecksumGenCrc32c over every file of
+    DB::VerifyFileChecksums, util/file_checksum_helper.h:22).  arena: a uint8
+    device tensor; offsets / lengths / inits: HOST sequences (the caller knows
+    its file sizes).  Returns a uint32 device tensor of len(offsets) entries
+    (`out`: the caller's own, at least that long; entries past them are left
+    alone)."""
+    _dev_u8(arena)
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+    lens = np.ascontiguousarray(lengths, dtype=np.uint64)
+    assert offs.ndim == 1 and offs.shape == lens.shape
+    n = len(offs)
+    ini = None
+    if inits is not None:
+        ini = np.ascontiguousarray(inits, dtype=np.uint32)
+        assert ini.shape == offs.shape
+    if out is None:
+        out = torch.empty(n, dtype=torch.uint32, device=arena.device)
+    assert out.device == arena.device
+    _out(out, n, 4)
+    check(lib().forst_crc32c_files(arena.data_ptr(), arena.numel(), offs.ctypes.data,
+                                   lens.ctypes.data, None if ini is None else ini.ctypes.data,
+                                   out.data_ptr(), n, _stream(stream)))
+    return out[:n]
 
 
 def crc32c_combine_batch(crc1, crc2, len2, out=None, stream=None):

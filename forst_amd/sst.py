@@ -131,3 +131,58 @@ def verify_files(files, file_names=None, stream=None, align=256):
     _rc(lib().forst_sst_verify_files(ptrs, sizes, doffs, ctypes.c_void_p(dev.data_ptr()),
                                      ctypes.c_uint64(pos), cnames, ctypes.c_uint64(n), out, st))
     return list(out)
+
+
+def file_checksum_string(crc):
+    """FileChecksumGenCrc32c::Finalize / GetChecksum: the 4 big-endian bytes"""
+    return int(crc & 0xFFFFFFFF).to_bytes(4, "big")
+
+
+def _stage(files, align):
+    hs = [_host(f) for f in files]
+    offs, pos = [], 0
+    for a in hs:
+        offs.append(pos)
+        pos += (len(a) + align - 1) // align * align
+    arena = np.zeros(max(pos, 1), dtype=np.uint8)
+    for a, o in zip(hs, offs):
+        arena[o:o + len(a)] = a
+    return torch.from_numpy(arena).to("cuda"), offs, [len(a) for a in hs]
+
+
+def file_checksums(files=None, arena=None, offsets=None, lengths=None, stream=None, align=256):
+    """FileChecksumGenCrc32c of every file in ONE call (forst_crc32c_files):
+    the whole-file CRC32C that DB::VerifyFileChecksums compares
+    (db/db_impl/db_impl.cc:6254-6402).  Either `files` (host bytes, staged in
+    one device arena here) or a device `arena` with host `offsets` / `lengths`
+    -- the arena verify_files staged.  Returns a list of unmasked CRCs."""
+    from . import engine
+    if arena is None:
+        arena, offsets, lengths = _stage(files, align)
+    out = engine.crc32c_files(arena, offsets, lengths, stream=stream)
+    if stream is not None:  # (the copy below waits for the current stream only)
+        torch.cuda.synchronize()
+    return [int(v) for v in out.cpu().view(torch.int32).numpy().view(np.uint32)]
+
+
+def verify_file_checksums(expected, files=None, file_names=None, arena=None, offsets=None,
+                          lengths=None, stream=None, align=256):
+    """DBImpl::VerifyFullFileChecksum per file (db_impl.cc:6373-6402):
+    expected[i] = the recorded 4-byte checksum string, b"" (kUnknownFileChecksum)
+    to skip the file.  Returns one message per file: "OK", or the reference's
+    "Corruption: <name> file checksum mismatch, expecting <HEX>, but actual <HEX>"."""
+    if arena is None:
+        arena, offsets, lengths = _stage(files, align)
+    n = len(offsets)
+    assert len(expected) == n
+    names = file_names or [f"{i:06d}.sst" for i in range(n)]
+    todo = [i for i in range(n) if len(expected[i])]
+    crcs = file_checksums(arena=arena, offsets=[offsets[i] for i in todo],
+                          lengths=[lengths[i] for i in todo], stream=stream)
+    out = ["OK"] * n
+    for i, crc in zip(todo, crcs):
+        actual = file_checksum_string(crc)
+        if actual != bytes(expected[i]):
+            out[i] = (f"Corruption: {names[i]} file checksum mismatch, expecting "
+                      f"{bytes(expected[i]).hex().upper()}, but actual {actual.hex().upper()}")
+    return out

@@ -12,6 +12,8 @@ from ._lib import ForstError, lib
 
 SINK = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8),
                         ctypes.c_uint64)
+SINK_CRC = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8),
+                            ctypes.c_uint64, ctypes.c_uint32)
 
 
 def _check(rc):
@@ -21,14 +23,23 @@ def _check(rc):
 
 
 class TrailerWriter:
-    """Writes blocks in builder order into `self.out` (the file bytes)."""
+    """Writes blocks in builder order into `self.out` (the file bytes).
+
+    file_checksum=True (or an int: the running checksum of whatever precedes
+    start_offset) keeps FileChecksumGenCrc32c's value over the emitted bytes
+    (`file_checksum`, `file_checksum_string` after flush() / footer());
+    crc_sink=True hands every piece over with crc32c::Value of exactly its
+    bytes (WritableFileWriter::Append's crc32c_checksum).  `self.pieces`
+    lists the sink calls as (offset in out, length, crc or None)."""
 
     def __init__(self, ctype, base_context_checksum=0, start_offset=0, block_align=0,
-                 window_bytes=0, stream=None):
+                 window_bytes=0, stream=None, file_checksum=False, crc_sink=False):
         self.out = bytearray()
         self.chunks = 0
+        self.pieces = []
 
         def sink(_arg, data, n):
+            self.pieces.append((len(self.out), n, None))
             self.out += ctypes.string_at(data, n)
             self.chunks += 1
             return 0
@@ -41,6 +52,31 @@ class TrailerWriter:
                                                ctypes.cast(self._sink, ctypes.c_void_p), None, s,
                                                ctypes.byref(h)))
         self._h = h
+        if crc_sink:
+            def sink_crc(_arg, data, n, crc):
+                self.pieces.append((len(self.out), n, crc))
+                self.out += ctypes.string_at(data, n)
+                self.chunks += 1
+                return 0
+
+            self._sink_crc = SINK_CRC(sink_crc)  # keep alive
+            _check(lib().forst_trailer_writer_set_crc_sink(
+                h, ctypes.cast(self._sink_crc, ctypes.c_void_p), None))
+        if file_checksum is not False and file_checksum is not None:
+            init = 0 if file_checksum is True else int(file_checksum)
+            _check(lib().forst_trailer_writer_enable_file_checksum(h, init & 0xFFFFFFFF))
+
+    @property
+    def file_checksum(self):
+        c = ctypes.c_uint32()
+        _check(lib().forst_trailer_writer_file_checksum(self._h, ctypes.byref(c), None))
+        return c.value
+
+    @property
+    def file_checksum_string(self):
+        be = (ctypes.c_uint8 * 4)()
+        _check(lib().forst_trailer_writer_file_checksum(self._h, None, be))
+        return bytes(be)
 
     def add(self, block, compression_type=0, is_data_block=True):
         """-> BlockHandle (offset, size), known before the trailer is computed"""

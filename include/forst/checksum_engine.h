@@ -183,6 +183,30 @@ std::vector<Status> VerifySstFilesChecksums(BlockChecksumEngine& engine,
                                             const uint8_t* dev_arena, uint64_t arena_len,
                                             std::vector<SstVerifyReport>* reports = nullptr);
 
+// DB::VerifyFileChecksums (DBImpl::VerifyChecksumInternal(use_file_checksum =
+// true), db/db_impl/db_impl.cc:6254-6402; the same pass at ingestion,
+// db/external_sst_file_ingestion_job.cc:222, :1072) over the files of a device
+// arena: FileChecksumGenCrc32c (util/file_checksum_helper.h:22-48) of every
+// file in ONE forst_crc32c_files call.  Only dev_offset, file_size and
+// file_name of each SstFileRef are used.  Synchronises the stream.
+// FileChecksums: the unmasked crc32c::Value per file (*status: why all are 0).
+std::vector<uint32_t> FileChecksums(BlockChecksumEngine& engine,
+                                    const std::vector<SstFileRef>& files, const uint8_t* dev_arena,
+                                    uint64_t arena_len, Status* status = nullptr);
+// expected[i] = the checksum string recorded for file i (FileMetaData::
+// file_checksum).  Each Status is what DBImpl::VerifyFullFileChecksum returns:
+// OK for kUnknownFileChecksum (empty: the file is not read), else OK or
+// Corruption("<name> file checksum mismatch, expecting <HEX>, but actual <HEX>").
+std::vector<Status> VerifyFullFileChecksums(BlockChecksumEngine& engine,
+                                            const std::vector<SstFileRef>& files,
+                                            const uint8_t* dev_arena, uint64_t arena_len,
+                                            const std::vector<std::string>& expected);
+// FileChecksumGenCrc32c::Finalize / GetChecksum: the 4 big-endian bytes of a
+// CRC, back again (false unless 4 bytes), and Slice::ToString(true) of a string
+std::string FileChecksumToString(uint32_t crc);
+bool FileChecksumFromString(const std::string& s, uint32_t* crc);
+std::string FileChecksumHex(const std::string& s);
+
 // Write-side batching for flush and compaction:
 // BlockBasedTableBuilder::WriteMaybeCompressedBlock
 // (table/block_based/block_based_table_builder.cc:1311-1360) with the trailer
@@ -203,9 +227,19 @@ class GpuTrailerWriter {
     bool block_align = false;            // BlockBasedTableOptions::block_align
     uint64_t alignment = 4096;
     uint64_t window_bytes = 32ull << 20;  // blocks per GPU launch (bytes)
+    // FileChecksumGenCrc32c (util/file_checksum_helper.h:22-48) kept running
+    // over every byte handed to the sink: WritableFileWriter::UpdateFileChecksum
+    // (file/writable_file_writer.cc:731) without the host pass
+    bool file_checksum = false;
+    uint32_t file_checksum_init = 0;  // the running checksum of whatever precedes start_offset
   };
   using Sink = std::function<Status(const char* data, size_t n)>;
+  // ... with crc32c::Value(data, n) (unmasked) of exactly the bytes handed
+  // over: WritableFileWriter::Append's crc32c_checksum argument
+  // (file/writable_file_writer.cc:45-59, :100-131)
+  using SinkWithCrc = std::function<Status(const char* data, size_t n, uint32_t crc32c)>;
   GpuTrailerWriter(const Options& opt, Sink sink, void* hip_stream = nullptr);
+  GpuTrailerWriter(const Options& opt, SinkWithCrc sink, void* hip_stream = nullptr);
   ~GpuTrailerWriter();
   GpuTrailerWriter(const GpuTrailerWriter&) = delete;
   GpuTrailerWriter& operator=(const GpuTrailerWriter&) = delete;
@@ -219,14 +253,26 @@ class GpuTrailerWriter {
                      uint64_t index_offset, uint64_t index_size);
   uint64_t offset() const { return offset_; }  // r->get_offset()
   const ChecksumStats& stats() const { return stats_; }
+  // Options::file_checksum: the checksum of the bytes handed to the sink so
+  // far (valid after Flush() or WriteFooter()), and the 4 big-endian bytes
+  // FileChecksumGenCrc32c::Finalize() / GetChecksum() give for it
+  uint32_t file_checksum() const { return file_crc_; }
+  std::string FileChecksumString() const;
+  // the same two switches after construction, before the first AddBlock
+  Status EnableFileChecksum(uint32_t init);
+  Status SetCrcSink(SinkWithCrc sink);
 
  private:
   struct Window;
+  bool want_crc() const { return opt_.file_checksum || static_cast<bool>(crc_sink_); }
+  Status Emit(const uint8_t* data, uint64_t n, uint32_t crc);
   Status Reserve(Window& w, uint64_t bytes, uint64_t blocks);
   Status Launch(Window& w);
   Status Retire(Window& w);
   Options opt_;
   Sink sink_;
+  SinkWithCrc crc_sink_;
+  uint32_t file_crc_ = 0;
   void* stream_;
   uint64_t offset_;
   Window* win_[2];

@@ -74,4 +74,15 @@ inline Status FromForst(const ROCKSDB_NAMESPACE::Status& s) {
   }
 }
 
+// DBImpl::VerifyFullFileChecksum's Status per file (checksum_engine.h
+// VerifyFullFileChecksums), in the reference's vocabulary
+inline std::vector<ROCKSDB_NAMESPACE::Status> VerifyFullFileChecksumsForst(
+    BlockChecksumEngine& engine, const std::vector<SstFileRef>& files, const uint8_t* dev_arena,
+    uint64_t arena_len, const std::vector<std::string>& expected) {
+  std::vector<ROCKSDB_NAMESPACE::Status> out;
+  for (const Status& s : VerifyFullFileChecksums(engine, files, dev_arena, arena_len, expected))
+    out.push_back(ToForst(s));
+  return out;
+}
+
 }  // namespace forst_gpu

@@ -30,6 +30,8 @@
  *                                  (util/file_checksum_helper.h:22) and the
  *                                  WritableFileWriter handoff CRC
  *                                  (file/writable_file_writer.cc:100-212)
+ *   forst_crc32c_files          <- FileChecksumGenCrc32c over a set of files
+ *                                  (util/file_checksum_helper.h:22), one call
  *   forst_crc32c_combine[_batch]<- crc32c::Crc32cCombine (util/crc32c.h:32,
  *                                  crc32c.cc:1279)
  *   forst_wal_verify_batch      <- log::Reader::ReadPhysicalRecord CRC check
@@ -164,6 +166,17 @@ int forst_crc32c_batch(const uint8_t* base, uint64_t base_len,
  * crc32c::Value. */
 int forst_crc32c_buffer(const uint8_t* base, uint64_t len, uint32_t init, uint32_t* out,
                         void* stream);
+
+/* Whole-file CRC32C of a set of files in one call (FileChecksumGenCrc32c,
+ * util/file_checksum_helper.h:22-48; DB::VerifyFileChecksums):
+ * out[i] (device) = crc32c::Extend(inits ? inits[i] : 0, arena + offsets[i], lengths[i]),
+ * unmasked.  offsets / lengths / inits are HOST arrays (the caller knows its file sizes);
+ * they may be reused as soon as the call returns.  Any byte alignment, any 64-bit length,
+ * length 0 gives the init.  Ranges outside [0, arena_len) -> FORST_EINVAL before any launch.
+ * Asynchronous on `stream`; a number of launches that does not depend on n_files. */
+int forst_crc32c_files(const uint8_t* arena, uint64_t arena_len, const uint64_t* offsets,
+                       const uint64_t* lengths, const uint32_t* inits, uint32_t* out,
+                       uint64_t n_files, void* stream);
 
 /* out[i] = crc32c::Crc32cCombine(crc1[i], crc2[i], len2[i]) (device arrays). */
 int forst_crc32c_combine_batch(const uint32_t* crc1, const uint32_t* crc2,
@@ -578,6 +591,21 @@ int forst_trailer_writer_flush(forst_trailer_writer* w);
 int forst_trailer_writer_footer(forst_trailer_writer* w, uint32_t format_version,
                                 uint64_t metaindex_offset, uint64_t metaindex_size,
                                 uint64_t index_offset, uint64_t index_size);
+/* Between open and the first add (FORST_EINVAL later):
+ *  - enable_file_checksum: keep FileChecksumGenCrc32c's running value
+ *    (util/file_checksum_helper.h:22-48) over every byte handed to the sink,
+ *    starting from `init` (the checksum of whatever precedes start_offset);
+ *  - set_crc_sink: hand the bytes to `sink` instead, with crc32c::Value (unmasked)
+ *    of exactly those bytes -- WritableFileWriter::Append's crc32c_checksum.
+ * Either makes a window's CRC come from its device copy, in the same readback
+ * as the block checksums.  file_checksum: the value after the last flush /
+ * footer and (be4, nullable) the 4 big-endian bytes Finalize() stores. */
+typedef int (*forst_sink_crc_fn)(void* arg, const uint8_t* data, uint64_t n, uint32_t crc32c);
+int forst_trailer_writer_enable_file_checksum(forst_trailer_writer* w, uint32_t init);
+int forst_trailer_writer_set_crc_sink(forst_trailer_writer* w, forst_sink_crc_fn sink,
+                                      void* sink_arg);
+int forst_trailer_writer_file_checksum(const forst_trailer_writer* w, uint32_t* crc,
+                                       uint8_t be4[4]);
 uint64_t forst_trailer_writer_offset(const forst_trailer_writer* w);
 int forst_trailer_writer_close(forst_trailer_writer* w); /* flushes, frees */
 const char* forst_trailer_writer_last_error(void);

@@ -1,0 +1,25 @@
+"""The whole-file checksum side of the C++ host shim on the GPU
+(tests/cpp/filecrc_selftest.cc): FileChecksums / VerifyFullFileChecksums with
+DBImpl::VerifyFullFileChecksum's Status text, the checksum-string helpers,
+GpuTrailerWriter's file checksum and SinkWithCrc, and the C setters."""
+import os
+import subprocess
+
+import pytest
+
+import forst_amd
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_filecrc_shim_on_gpu(tmp_path):
+    libdir = os.path.dirname(forst_amd.LIB_PATH)
+    exe = str(tmp_path / "filecrc_selftest")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", f"-I{ROOT}/include", "-I/opt/rocm/include",
+                           "-D__HIP_PLATFORM_AMD__",
+                           os.path.join(ROOT, "tests", "cpp", "filecrc_selftest.cc"), "-o", exe,
+                           f"-L{libdir}", "-lforst_checksum", "-L/opt/rocm/lib", "-lamdhip64",
+                           f"-Wl,-rpath,{libdir}:/opt/rocm/lib", "-lpthread"])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "PASS" in r.stdout, r.stdout + r.stderr
