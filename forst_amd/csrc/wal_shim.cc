@@ -30,6 +30,7 @@ Status FromHip(hipError_t e, const char* what) {
   return Status::IOError(std::string(what) + ": " + hipGetErrorString(e));
 }
 bool recyclable_type(uint32_t t) { return (t >= 5 && t <= 8) || t == 11; }  // log_format.h:20-41
+bool control_type(uint32_t t) { return t >= 9 && t <= 11; }  // :37-41
 uint64_t align8(uint64_t x) { return (x + 7) & ~uint64_t{7}; }
 }  // namespace
 
@@ -140,8 +141,9 @@ Status WalRecovery::Recover(const uint8_t* d_log, const uint8_t* host_log, uint6
 // The record's fragments are consecutive physical records from the reader's
 // position at LastRecordOffset (ReadRecord consumes them back to back; a
 // < header-size block tail, or a recyclable log's zero-filled one, is skipped
-// as ReadPhysicalRecord skips it).  Reports made during this ReadRecord call
-// lie before the end of its last fragment.
+// as ReadPhysicalRecord skips it), behind the control record (types 9-11) at
+// that position when one lay between the record's fragments.  Reports made
+// during this ReadRecord call lie before the end of its last fragment.
 bool WalRecovery::Next(WalRecord* r) {
   if (!status_.ok()) return false;
   if (next_rec_ >= off_.size()) {
@@ -155,7 +157,7 @@ bool WalRecovery::Next(WalRecord* r) {
   scratch_.clear();
   const char* single = nullptr;
   uint64_t got = 0;
-  for (uint32_t f = 0; f < nf; ++f) {
+  for (uint32_t f = 0; f < nf;) {
     for (;;) {  // block tails the writer padded
       const uint64_t left = kBlockSize - p % kBlockSize;
       if (left < kHeaderSize) {
@@ -174,6 +176,14 @@ bool WalRecovery::Next(WalRecord* r) {
     const uint32_t hs = recyclable_type(t) ? kRecyclableHeaderSize : kHeaderSize;
     const uint64_t n = static_cast<uint64_t>(host_[p + 4]) | static_cast<uint64_t>(host_[p + 5]) << 8;
     if (p + hs + n > len_) break;
+    if (control_type(t)) {
+      // a control record between the fragments: the reader clears scratch and
+      // moves LastRecordOffset to it (log_reader.cc:167-213), so it stands at
+      // the record's offset, is in no record's bytes and is not in n_fragments
+      p += hs + n;
+      continue;
+    }
+    ++f;
     const char* payload = reinterpret_cast<const char*>(host_ + p + hs);
     if (nf == 1)
       single = payload;

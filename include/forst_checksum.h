@@ -310,7 +310,13 @@ typedef struct forst_wal_records {
   uint64_t* offset;       /* Reader::LastRecordOffset of the record */
   uint64_t* length;       /* logical record bytes */
   uint64_t* hash;         /* XXH3_64bits(record) */
-  uint32_t* n_fragments;  /* physical records */
+  uint32_t* n_fragments;  /* the physical records whose payload is in the record:
+                             1 for a Full record; a First counts 1, every Middle /
+                             Last appended to it 1 more; a control record (types
+                             9-11) between the fragments clears the count with the
+                             reader's scratch (:167-213) and becomes the record's
+                             offset, so it and the fragments in front of it are not
+                             counted (First, control, Last: 1, not 3) */
 } forst_wal_records;
 typedef struct forst_wal_reports {
   uint64_t* offset;  /* reader position of the physical record / event */
@@ -320,9 +326,19 @@ typedef struct forst_wal_reports {
 } forst_wal_reports;
 typedef struct forst_wal_recover_result {
   uint64_t n_records, n_reports;
-  uint64_t n_physical;   /* physical records parsed by the walk */
-  uint64_t stop_offset;  /* reader position where reading ended */
-  uint32_t stop_reason;  /* forst_wal_stop_reason */
+  uint64_t n_physical;   /* headers the header chain reaches, over EVERY 32 KiB block of
+                            the log, whatever their CRC and wherever reading ended.
+                            A block's chain ends at the first of: fewer than
+                            header-size bytes left; header + length past the block
+                            end; zero type with zero length; a recyclable header of
+                            another log number (counted and stepped over in
+                            kSkipAnyCorruptedRecords) */
+  uint64_t stop_offset;  /* the reader's position (end_of_buffer_offset - buffer size)
+                            in front of the ReadPhysicalRecord call whose result made
+                            ReadRecord return false: the offending header, the
+                            truncated tail, or the log's end.  Not LastRecordEnd(),
+                            which lies behind what that call consumed */
+  uint32_t stop_reason;  /* forst_wal_stop_reason of that result */
   uint32_t truncated;    /* a count exceeded its capacity */
   uint32_t unsupported;  /* a kSetCompressionType record names kZSTD (FORST_EUNSUPPORTED) */
   uint32_t reserved;

@@ -12,7 +12,10 @@ Record types db/log_format.h:20-43; recovery modes include/rocksdb/options.h
 Pinned against the reference reader itself: tests/golden/gen_wal_golden.py
 drives the reference's compiled log::Reader over the scenario logs of
 tests/walcases.py and commits its transcripts (tests/golden/wal_reader.json);
-tests/test_wal_golden.py checks this restatement against them.  Behaviours
+tests/test_wal_golden.py checks this restatement against them, the reader's
+end state and the order of its Corruption calls among the records included
+(read_all_ex, which also gives forst_wal_recover_batch's fragment counts and
+stop fields in reader terms; n_physical restates the walk).  Behaviours
 the pinning brought out, restated here as the reference has them:
   * the record type is read from a `const char*` into `unsigned int`
     (:466-469), so a type byte >= 0x80 sign-extends ("unknown record type
@@ -45,6 +48,9 @@ kZSTD = 7
 # WALRecoveryMode (include/rocksdb/options.h)
 kTolerateCorruptedTailRecords, kAbsoluteConsistency, kPointInTimeRecovery, \
     kSkipAnyCorruptedRecords = 0, 1, 2, 3
+
+# forst_wal_stop_reason (include/forst_checksum.h): why read_record returned None
+STOP_EOF, STOP_OLD_RECORD, STOP_TRUNCATED_HEADER, STOP_TRUNCATED_BODY, STOP_RECYCLED_TAIL = range(5)
 
 
 class Unsupported(Exception):
@@ -83,6 +89,9 @@ class Reader:
         self.last_record_offset = 0
         self.reports = []  # (bytes, reason, reader position of the physical record)
         self.cur_phys = 0
+        # what read_all_ex adds to the record triple, in reader terms:
+        self.n_fragments = 0    # physical records whose payload is in scratch
+        self.stop_reason = None  # forst_wal_stop_reason once read_record returned None
 
     def _size(self):
         return self.buf_hi - self.buf_lo
@@ -165,6 +174,7 @@ class Reader:
                     self._report(len(scratch), "partial record without end(1)")
                 self.last_record_offset = phys
                 self.first_record_read = True
+                self.n_fragments = 1
                 return phys, frag, O.xxh3_64(frag)
             if rt in (kFirstType, kRecyclableFirstType):
                 if in_frag and scratch:
@@ -173,6 +183,7 @@ class Reader:
                 self.hash.update(frag)
                 prospective = phys
                 scratch = frag
+                self.n_fragments = 1
                 in_frag = True
                 continue
             if rt in (kMiddleType, kRecyclableMiddleType):
@@ -181,6 +192,7 @@ class Reader:
                 else:
                     self.hash.update(frag)
                     scratch += frag
+                    self.n_fragments += 1
                 continue
             if rt in (kLastType, kRecyclableLastType):
                 if not in_frag:
@@ -189,6 +201,7 @@ class Reader:
                 self.hash.update(frag)
                 self.last_record_offset = prospective
                 self.first_record_read = True
+                self.n_fragments += 1
                 return prospective, scratch + frag, self.hash.digest()
             if rt == kSetCompressionType:
                 if self.compression_type_record_read:
@@ -197,6 +210,7 @@ class Reader:
                     self._report(len(frag), "SetCompressionType not the first record")
                 prospective = phys
                 scratch = b""
+                self.n_fragments = 0
                 self.last_record_offset = prospective
                 # CompressionTypeRecord::DecodeFrom (util/compression.h:1716):
                 # GetFixed32 consumes 4 bytes; CompressionType is an 8-bit enum
@@ -217,6 +231,7 @@ class Reader:
                                  "interspersed partial record")
                 prospective = phys
                 scratch = b""
+                self.n_fragments = 0
                 self.last_record_offset = prospective
                 # UserDefinedTimestampSizeRecord::DecodeFrom (util/udt_util.h:46)
                 if len(frag) % 6:
@@ -240,40 +255,46 @@ class Reader:
             if rt == kBadHeader:
                 if strict:
                     self._report(drop, "truncated header")
+                self.stop_reason = STOP_TRUNCATED_HEADER
                 rt = kEof
             if rt == kEof:
                 if in_frag and strict:
                     self._report(len(scratch), "error reading trailing data")
+                if self.stop_reason is None:
+                    self.stop_reason = STOP_EOF
                 return None
             if rt == kOldRecord:
                 if mode != kSkipAnyCorruptedRecords:
                     if in_frag and strict:
                         self._report(len(scratch), "error reading trailing data")
+                    self.stop_reason = STOP_OLD_RECORD
                     return None
                 rt = kBadRecord
             if rt == kBadRecord:
                 if in_frag:
                     self._report(len(scratch), "error in middle of record")
-                    in_frag, scratch = False, b""
+                    in_frag, scratch, self.n_fragments = False, b"", 0
                 continue
             if rt == kBadRecordLen:
                 if self.eof:
                     if strict:
                         self._report(drop, "truncated record body")
+                    self.stop_reason = STOP_TRUNCATED_BODY
                     return None
             if rt in (kBadRecordLen, kBadRecordChecksum):
                 if self.recycled and mode == kTolerateCorruptedTailRecords:
+                    self.stop_reason = STOP_RECYCLED_TAIL
                     return None
                 self._report(drop, "bad record length" if rt == kBadRecordLen
                              else "checksum mismatch")
                 if in_frag:
                     self._report(len(scratch), "error in middle of record")
-                    in_frag, scratch = False, b""
+                    in_frag, scratch, self.n_fragments = False, b"", 0
                 continue
             # unknown record type (:308-316)
             self._report(len(frag) + (len(scratch) if in_frag else 0),
                          "unknown record type %u" % rt)
-            in_frag, scratch = False, b""
+            in_frag, scratch, self.n_fragments = False, b"", 0
 
 
 def resume_at(reader, pos, recycled=False):
@@ -312,3 +333,69 @@ def read_all(log, log_number=0, mode=kPointInTimeRecovery):
         off, payload, h = got
         recs.append((off, len(payload), h))
     return recs, r.reports
+
+
+def read_all_ex(log, log_number=0, mode=kPointInTimeRecovery):
+    """Everything forst_wal_recover_batch returns, in reader terms:
+      records        (offset, length, checksum, n_fragments) per ReadRecord that
+                     returned true; n_fragments = the physical records whose
+                     payload is in the returned record (Full: 1; First sets 1,
+                     an appended Middle / Last adds 1; a control record, types
+                     9-11, clears it with scratch; what clears
+                     in_fragmented_record discards it)
+      payload_xxh3   XXH3_64bits of each returned record's bytes, taken afresh
+                     (the reader's own checksum can cover more: see above)
+      reports        (bytes, reason, reader position) in call order
+      reports_before per record, how many Corruption calls the reporter had
+                     seen when the record was returned, then the final count
+      stop_offset    the reader position (end_of_buffer_offset - buffer size)
+                     in front of the ReadPhysicalRecord call whose result made
+                     ReadRecord return false
+      stop_reason    the forst_wal_stop_reason of that result
+      end            (LastRecordEnd(), IsEOF()) after that"""
+    r = Reader(log, log_number)
+    recs, before, fresh = [], [], []
+    while True:
+        got = r.read_record(mode)
+        if got is None:
+            break
+        off, payload, h = got
+        recs.append((off, len(payload), h, r.n_fragments))
+        fresh.append(O.xxh3_64(payload))
+        before.append(len(r.reports))
+    before.append(len(r.reports))
+    return {"records": recs, "payload_xxh3": fresh, "reports": r.reports,
+            "reports_before": before,
+            "stop_offset": r.cur_phys, "stop_reason": r.stop_reason,
+            "end": (r.end_of_buffer_offset - r._size(), r.eof)}
+
+
+def n_physical(log, log_number=0, mode=kPointInTimeRecovery):
+    """forst_wal_recover_result.n_physical: the headers the header chain
+    reaches, summed over every 32 KiB block of the log.  The chain starts at
+    each block start and ends at the first of: fewer than header-size bytes
+    left (7, or 11 under a recyclable type); header + length past the block
+    end; zero type with zero length; a recyclable header of another log number
+    (counted and stepped over in kSkipAnyCorruptedRecords).  CRCs and where
+    the reader stopped play no part."""
+    log = bytes(log)
+    n = 0
+    for start in range(0, len(log), kBlockSize):
+        end = min(start + kBlockSize, len(log))
+        pos = start
+        while end - pos >= kHeaderSize:
+            length = log[pos + 4] | (log[pos + 5] << 8)
+            rtype = log[pos + 6]
+            recyc = kRecyclableFullType <= rtype <= kRecyclableLastType or \
+                rtype == kRecyclableUserDefinedTimestampSizeType
+            hs = kRecyclableHeaderSize if recyc else kHeaderSize
+            if end - pos < hs or hs + length > end - pos:
+                break
+            if recyc and int.from_bytes(log[pos + 7:pos + 11], "little") != log_number:
+                if mode != kSkipAnyCorruptedRecords:
+                    break
+            elif rtype == kZeroType and length == 0:
+                break
+            n += 1
+            pos += hs + length
+    return n

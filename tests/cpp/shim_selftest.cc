@@ -3,6 +3,9 @@
 //   shim_selftest pure   host-only helpers (no GPU)
 //   shim_selftest gpu    BlockChecksumEngine write/verify on a real MI355X
 //   shim_selftest wal    WalWriteGroup framing + WalRecovery round trip
+//   shim_selftest walfile (<log> <expect> <log_number> <mode>)...
+//                        WalRecovery over log files: the records and reports a
+//                        caller replays, against the serial reader's transcript
 //   shim_selftest threads  4 host threads, one HIP stream each, interleaving
 //                        write-side, verify, WAL and raw-hash calls against
 //                        the engine's shared per-device scratch pool
@@ -12,6 +15,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <thread>
@@ -396,9 +400,126 @@ static void wal(bool recyclable) {
   (void)hipFree(d_log);
 }
 
+// What a ForSt caller replays from a log file: WalRecovery::Recover, then Next
+// to the end, as a transcript in call order --
+//   C <offset> <bytes> <text>     a report, in front of the record it precedes
+//   R <offset> <size> <n_fragments> <checksum> <XXH3 of r.data> <reports before>
+//   C ...                          the trailing reports
+//   S <status().ToString()>
+//   E <stop_offset> <stop_reason> <n_records> <n_reports> <n_physical>
+// printed under a "case" line and compared with the lines of <expect> (the
+// serial reader's, written by tests/test_gpu_shim.py).  The XXH3 of the bytes
+// handed out is taken with forst_xxh3_64_batch over a copy of them, so it is
+// not the checksum the recovery computed from the log.
+static bool read_file(const char* path, std::string* out) {
+  std::FILE* f = std::fopen(path, "rb");
+  if (!f) return false;
+  char buf[1 << 16];
+  size_t n;
+  out->clear();
+  while ((n = std::fread(buf, 1, sizeof(buf), f)) > 0) out->append(buf, n);
+  std::fclose(f);
+  return true;
+}
+
+static void walfile(const char* log_path, const char* expect_path, uint32_t log_number, int mode) {
+  std::string log, expect;
+  if (!read_file(log_path, &log) || !read_file(expect_path, &expect)) {
+    std::printf("FAIL cannot read %s / %s\n", log_path, expect_path);
+    ++g_fail;
+    return;
+  }
+  uint8_t* d_log = nullptr;
+  CHECK(hipMalloc(&d_log, log.size() + 256) == hipSuccess);
+  if (!log.empty())
+    CHECK(hipMemcpy(d_log, log.data(), log.size(), hipMemcpyHostToDevice) == hipSuccess);
+  WalRecovery rec;
+  const Status rs = rec.Recover(d_log, reinterpret_cast<const uint8_t*>(log.data()), log.size(),
+                                log_number, mode);
+  struct Line {
+    std::string text;
+    int64_t rec;       // an R line: the record whose XXH3 goes between text and tail; else -1
+    std::string tail;
+  };
+  std::vector<Line> lines;
+  std::string bytes;  // the records' bytes back to back, 8-byte aligned starts
+  std::vector<uint64_t> offs;
+  std::vector<uint32_t> lens;
+  char buf[256];
+  auto report = [&](const WalReport& p) {
+    std::snprintf(buf, sizeof(buf), "C %llu %llu ", static_cast<unsigned long long>(p.offset),
+                  static_cast<unsigned long long>(p.bytes));
+    lines.push_back({buf + p.Text(), -1, ""});
+  };
+  WalRecord r;
+  while (rs.ok() && rec.Next(&r)) {
+    for (const WalReport& p : r.reports_before) report(p);
+    std::snprintf(buf, sizeof(buf), "R %llu %zu %u %016llx", static_cast<unsigned long long>(r.offset),
+                  r.size, r.n_fragments, static_cast<unsigned long long>(r.checksum));
+    lines.push_back({buf, static_cast<int64_t>(offs.size()),
+                     " " + std::to_string(r.reports_before.size())});
+    bytes.resize((bytes.size() + 7) & ~size_t{7});
+    offs.push_back(bytes.size());
+    lens.push_back(static_cast<uint32_t>(r.size));
+    bytes.append(r.data, r.size);
+  }
+  for (const WalReport& p : rec.trailing_reports()) report(p);
+  std::vector<uint64_t> h(offs.size());
+  if (!offs.empty()) {
+    uint8_t* d_b = nullptr;
+    uint64_t *d_o = nullptr, *d_h = nullptr;
+    uint32_t* d_l = nullptr;
+    const size_t n = offs.size();
+    CHECK(hipMalloc(&d_b, bytes.size() + 256) == hipSuccess);
+    CHECK(hipMalloc(&d_o, n * 8) == hipSuccess && hipMalloc(&d_h, n * 8) == hipSuccess &&
+          hipMalloc(&d_l, n * 4) == hipSuccess);
+    if (!bytes.empty())
+      CHECK(hipMemcpy(d_b, bytes.data(), bytes.size(), hipMemcpyHostToDevice) == hipSuccess);
+    CHECK(hipMemcpy(d_o, offs.data(), n * 8, hipMemcpyHostToDevice) == hipSuccess);
+    CHECK(hipMemcpy(d_l, lens.data(), n * 4, hipMemcpyHostToDevice) == hipSuccess);
+    CHECK(forst_xxh3_64_batch(d_b, bytes.size() + 8, d_o, d_l, d_h, n, nullptr) == FORST_OK);
+    CHECK(hipDeviceSynchronize() == hipSuccess);
+    CHECK(hipMemcpy(h.data(), d_h, n * 8, hipMemcpyDeviceToHost) == hipSuccess);
+    (void)hipFree(d_b), (void)hipFree(d_o), (void)hipFree(d_h), (void)hipFree(d_l);
+  }
+  std::string got;
+  for (const Line& l : lines) {
+    got += l.text;
+    if (l.rec >= 0) {
+      std::snprintf(buf, sizeof(buf), " %016llx", static_cast<unsigned long long>(h[l.rec]));
+      got += buf + l.tail;
+    }
+    got += "\n";
+  }
+  const Status& s = rs.ok() ? rec.status() : rs;
+  got += "S " + s.ToString() + "\n";
+  const forst_wal_recover_result& res = rec.result();
+  std::snprintf(buf, sizeof(buf), "E %llu %u %llu %llu %llu\n",
+                static_cast<unsigned long long>(res.stop_offset), res.stop_reason,
+                static_cast<unsigned long long>(res.n_records),
+                static_cast<unsigned long long>(res.n_reports),
+                static_cast<unsigned long long>(res.n_physical));
+  got += buf;
+  std::printf("case %s %u %d\n%s", log_path, log_number, mode, got.c_str());
+  if (got != expect) {
+    std::printf("FAIL %s mode %d: transcript differs from %s\n", log_path, mode, expect_path);
+    ++g_fail;
+  }
+  (void)hipFree(d_log);
+}
+
 int main(int argc, char** argv) {
   const std::string mode = argc > 1 ? argv[1] : "pure";
   pure();
+  if (mode == "walfile") {  // walfile (<log> <expect> <log_number> <mode>)...
+    if (argc < 6 || (argc - 2) % 4) {
+      std::printf("usage: shim_selftest walfile (<log> <expect> <log_number> <mode>)...\n");
+      return 2;
+    }
+    for (int i = 2; i + 3 < argc; i += 4)
+      walfile(argv[i], argv[i + 1], static_cast<uint32_t>(std::strtoul(argv[i + 2], nullptr, 10)),
+              std::atoi(argv[i + 3]));
+  }
   if (mode == "gpu") gpu();
   if (mode == "threads") threads();
   if (mode == "wal") {

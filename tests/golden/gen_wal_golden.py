@@ -14,8 +14,11 @@ The logs are the scenario builders of tests/walcases.py (deterministic from
 their seeds; each log's SHA-256 is recorded so a test can prove it rebuilt
 the same bytes).  Committed: tests/golden/wal_reader.json.gz -- per log and
 WALRecoveryMode, every record (LastRecordOffset, length, record checksum),
-every Reporter::Corruption(bytes, Status::ToString()) call in order, and the
-reader position / EOF flag when ReadRecord returned false.
+every Reporter::Corruption(bytes, Status::ToString()) call in order, the
+reader position / EOF flag when ReadRecord returned false, and the call order
+of the two: "reports_before" = [record index, Corruption calls made during the
+ReadRecord call that returned it] for every record with a non-zero count, and
+"reports_after" = the calls made after the last record.
 
 Re-run:  python tests/golden/gen_wal_golden.py   (needs /root/reference + g++)
 """
@@ -65,11 +68,14 @@ def reader(path):
         n = ctypes.c_size_t()
         rc = L.ref_wal_read(bytes(log), len(log), ln, mode, out, cap, ctypes.byref(n))
         assert rc == 0
-        recs, reps, end = [], [], None
+        recs, reps, end, before, seen = [], [], None, [], 0
         for line in out.raw[:n.value].decode().splitlines():
             kind, rest = line[0], line[2:]
             if kind == "R":
                 o, n_, h = rest.split(" ")
+                if len(reps) > seen:  # the transcript is in call order: C lines before this R
+                    before.append([len(recs), len(reps) - seen])
+                seen = len(reps)
                 recs.append([int(o), int(n_), h])
             elif kind == "C":
                 b, text = rest.split(" ", 1)
@@ -77,7 +83,8 @@ def reader(path):
             else:
                 p, eof = rest.split(" ")
                 end = [int(p), int(eof)]
-        return {"records": recs, "reports": reps, "end": end}
+        return {"records": recs, "reports": reps, "end": end, "reports_before": before,
+                "reports_after": len(reps) - seen}
     return run
 
 

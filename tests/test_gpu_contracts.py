@@ -134,6 +134,34 @@ def test_recover_ample_capacity(group):
     print(f"ample-capacity (log, mode) cases [{group}]: {cases}")
 
 
+@pytest.mark.parametrize("recyclable", [False, True])
+def test_recover_stop_and_fragment_cases(recyclable):
+    """the small logs of walcases.stop_and_fragment_cases -- each stop cause at
+    a block start, mid-block, in the short last block and as the first record,
+    with and without a First open; the fragment-count sequences; empty and tiny
+    logs -- each uploaded once, all four modes, into sentinel-filled arrays:
+    every record (fragment count included), report and result scalar equals
+    the serial reader's, and nothing is stored behind the counts"""
+    reasons = set()
+    for name, log, ln in W.stop_and_fragment_cases(recyclable):
+        assert len(log) <= 6 * 32768
+        dlog = d(log)
+        for mode in T.MODES:
+            want = R.read_all_ex(log, ln, mode)
+            n, m = len(want["records"]), len(want["reports"])
+            recs, reps, res = recover_into(dlog, ln, mode, n + GUARD, m + GUARD)
+            T.compare([recs[k][:n] for k in REC_KEYS], [reps[k][:m] for k in REP_KEYS], res, log,
+                      ln, mode, name)
+            for k, size in C.REC_FIELDS:
+                C.untouched(recs[k], n, size, (name, mode, "records", k))
+            for k, size in C.REP_FIELDS:
+                C.untouched(reps[k], m, size, (name, mode, "reports", k))
+            reasons.add(res.stop_reason)
+    # (an old record and a recycled log's tolerated tail need recyclable headers)
+    assert reasons == {R.STOP_EOF, R.STOP_TRUNCATED_HEADER, R.STOP_TRUNCATED_BODY} | \
+        ({R.STOP_OLD_RECORD, R.STOP_RECYCLED_TAIL} if recyclable else set())
+
+
 @pytest.mark.parametrize("group", GROUPS)
 def test_recover_short_capacity_and_null_members(group):
     """the same logs and modes with the seven capacity pairs of

@@ -6,7 +6,10 @@ checksum) over the scenario logs of tests/walcases.py in all four
 WALRecoveryModes (tests/golden/gen_wal_golden.py).  The CPU test checks the
 oracle restatement (oracle/wal_reader.py) against them; the -m gpu test checks
 forst_wal_recover_batch against them directly, record for record and report
-for report (Status text included)."""
+for report (Status text included).  What the fixture cannot hold -- the
+fragment counts, the walk's n_physical, the stop position and reason -- comes
+from the restatement's read_all_ex, itself pinned here to the fixture's end
+state and call order."""
 import gzip
 import hashlib
 import json
@@ -37,6 +40,19 @@ REASONS = {1: "partial record without end(1)", 2: "partial record without end(2)
 
 def reason_text(code, rtype):
     return "unknown record type %u" % rtype if code == 11 else REASONS[code]
+
+
+def compare_result(res, want, log, log_number, mode, name):
+    """the result scalars against the serial reader (wal_reader.read_all_ex)
+    and the restated walk (wal_reader.n_physical); the arrays held everything"""
+    key = (name, mode)
+    assert res.n_records == len(want["records"]), (key, res.n_records, len(want["records"]))
+    assert res.n_reports == len(want["reports"]), (key, res.n_reports, len(want["reports"]))
+    assert res.stop_offset == want["stop_offset"], (key, res.stop_offset, want["stop_offset"])
+    assert res.stop_reason == want["stop_reason"], (key, res.stop_reason, want["stop_reason"])
+    n_phys = R.n_physical(log, log_number, mode)
+    assert res.n_physical == n_phys, (key, res.n_physical, n_phys)
+    assert res.truncated == 0 and res.unsupported == 0, (key, res.truncated, res.unsupported)
 
 
 def load():
@@ -79,6 +95,29 @@ def want(c, mode):
     return recs, reps
 
 
+_EX = {}
+
+
+def ex(c, log, mode):
+    """read_all_ex of a fixture log, computed once for the module"""
+    key = (c["family"], c["name"], c["recyclable"], mode)
+    if key not in _EX:
+        _EX[key] = R.read_all_ex(log.tobytes(), c["log_number"], mode)
+    return _EX[key]
+
+
+def want_order(c, mode):
+    """the reference's call order: Corruption calls made when each record was
+    returned, then the final count (the fixture stores the per-record counts)"""
+    m = c["modes"][str(mode)]
+    per = dict((i, k) for i, k in m["reports_before"])
+    out, seen = [], 0
+    for i in range(len(m["records"])):
+        seen += per.get(i, 0)
+        out.append(seen)
+    return out + [seen + m["reports_after"]]
+
+
 def test_fixture_covers_the_reader_outcomes(golden):
     """the transcripts exercise every report text the reader can produce"""
     texts = set()
@@ -101,6 +140,40 @@ def test_oracle_reader_matches_reference(golden):
                 (c["family"], c["name"], c["recyclable"], mode)
 
 
+def test_oracle_end_state_and_call_order_match_reference(golden):
+    """read_all_ex: the reference's records and reports as read_all, the reader's
+    LastRecordEnd() / IsEOF() after ReadRecord returned false, and the order
+    of the Corruption calls among the records, for all 55 logs x 4 modes"""
+    for c, log in golden:
+        for mode in range(4):
+            key = (c["family"], c["name"], c["recyclable"], mode)
+            x = ex(c, log, mode)
+            wr, wp = want(c, mode)
+            assert [r[:3] for r in x["records"]] == wr, key
+            assert [(b, "Corruption: " + t) for b, t, _ in x["reports"]] == wp, key
+            end = c["modes"][str(mode)]["end"]
+            assert [x["end"][0], int(x["end"][1])] == end, (key, x["end"], end)
+            assert x["reports_before"] == want_order(c, mode), key
+            assert 0 <= x["stop_offset"] <= x["end"][0] <= len(log), key
+
+
+def test_the_logs_reach_every_stop_reason(golden):
+    """the reference-pinned logs alone end reading for each of the five
+    forst_wal_stop_reasons, and for each one that can end reading before the
+    log does (all but a truncated body, which needs the log's end) more than
+    one log block in front of the end"""
+    seen, mid = set(), set()
+    for c, log in golden:
+        for mode in range(4):
+            x = ex(c, log, mode)
+            seen.add(x["stop_reason"])
+            if x["stop_offset"] + R.kBlockSize < len(log):
+                mid.add(x["stop_reason"])
+    assert seen == {R.STOP_EOF, R.STOP_OLD_RECORD, R.STOP_TRUNCATED_HEADER,
+                    R.STOP_TRUNCATED_BODY, R.STOP_RECYCLED_TAIL}, seen
+    assert mid == seen - {R.STOP_TRUNCATED_BODY}, mid
+
+
 @pytest.mark.gpu
 def test_gpu_recovery_matches_reference(golden):
     import torch
@@ -121,6 +194,12 @@ def test_gpu_recovery_matches_reference(golden):
                   zip(rep["bytes"].cpu().tolist(), rep["reason"].cpu().tolist(),
                       rep["type"].cpu().tolist())]
             assert gp == wp, key
+            # ... and what the fixture does not hold, against the serial reader
+            x = ex(c, log, mode)
+            assert [r[:3] for r in x["records"]] == wr, key
+            assert rec["n_fragments"].cpu().tolist() == [r[3] for r in x["records"]], key
+            assert rep["offset"].cpu().tolist() == [p for _, _, p in x["reports"]], key
+            compare_result(res, x, log, c["log_number"], mode, key)
 
 
 EMU_CASES = [("scenarios", "crc", False), ("pseudo", "mixed", True), ("pseudo", "partials", False),
@@ -141,8 +220,13 @@ def test_emulated_recovery_matches_reference(golden):
     by_key = {(c["family"], c["name"], c["recyclable"]): (c, log) for c, log in golden}
     for key in EMU_CASES:
         c, log = by_key[key]
-        (ro, rl, rh, _), (_, pb, pr, pt), res = E.wal_recover(log, c["log_number"], 2)
+        (ro, rl, rh, rn), (po, pb, pr, pt), res = E.wal_recover(log, c["log_number"], 2)
         wr, wp = want(c, 2)
         assert [(int(a), int(b), int(h)) for a, b, h in zip(ro, rl, rh)] == wr, key
         assert [(int(b), "Corruption: " + reason_text(int(r), int(t) & 0xFFFFFFFF))
                 for b, r, t in zip(pb, pr, pt)] == wp, key
+        x = ex(c, log, 2)
+        assert [r[:3] for r in x["records"]] == wr, key
+        assert [int(f) for f in rn] == [r[3] for r in x["records"]], key
+        assert [int(p) for p in po] == [p for _, _, p in x["reports"]], key
+        compare_result(res, x, log, c["log_number"], 2, key)

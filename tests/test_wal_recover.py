@@ -14,7 +14,7 @@ import pytest
 
 import walcases as W
 from oracle import wal_reader as R
-from test_wal_golden import reason_text
+from test_wal_golden import compare_result, reason_text
 
 MODES = [R.kTolerateCorruptedTailRecords, R.kAbsoluteConsistency, R.kPointInTimeRecovery,
          R.kSkipAnyCorruptedRecords]
@@ -22,15 +22,21 @@ scenarios = W.scenarios
 
 
 def compare(got_recs, got_reps, res, log, log_number, mode, name):
-    want_recs, want_reps = R.read_all(log, log_number, mode)
+    want = R.read_all_ex(log, log_number, mode)
+    want_recs, want_reps = want["records"], want["reports"]
     go, gl, gh, gn = (np.asarray(x) for x in got_recs)
     assert len(go) == len(want_recs), (name, mode, len(go), len(want_recs))
     assert [(int(a), int(b), int(c) & (2**64 - 1)) for a, b, c in zip(go, gl, gh)] == \
-        [(o, n, h) for o, n, h in want_recs], (name, mode)
+        [(o, n, h) for o, n, h, _ in want_recs], (name, mode)
+    nf = [(o, f) for o, _, _, f in want_recs]
+    assert [(int(a), int(f)) for a, f in zip(go, gn)] == nf, \
+        (name, mode, [(g, w) for g, w in zip(zip(go.tolist(), gn.tolist()), nf)
+                      if g != w][:5])
     po, pb, pr, pt = (np.asarray(x) for x in got_reps)
     got = [(int(b), reason_text(int(r), int(t) & 0xFFFFFFFF), int(o))
            for o, b, r, t in zip(po, pb, pr, pt)]
     assert got == [(b, r, p) for b, r, p in want_reps], (name, mode, got[:5], want_reps[:5])
+    compare_result(res, want, log, log_number, mode, name)
 
 
 def _emu():
@@ -354,6 +360,9 @@ def test_full_size_c5_recovery(recyclable):
     for mode in MODES:
         got, _, res = recover(mode)
         assert res.n_records == n and res.n_reports == 0, (mode, res.n_records, res.n_reports)
+        # a clean log is read to its end: kEof with the reader at the last byte
+        assert (res.stop_reason, res.stop_offset) == (R.STOP_EOF, w.total), \
+            (mode, res.stop_reason, res.stop_offset, w.total)
         for k in keys:
             assert (got[k] == exp[k]).all(), (mode, k)
 
@@ -389,6 +398,20 @@ def test_long_control_runs_on_emulator(recyclable):
     unfinished First and between Full records, every mode"""
     E = _emu()
     for name, log, ln in W.long_control_runs(recyclable):
+        for mode in MODES:
+            recs, reps, res = E.wal_recover(log, ln, mode)
+            compare(recs, reps, res, log, ln, mode, name)
+
+
+@pytest.mark.parametrize("recyclable", [False, True])
+def test_stop_and_fragment_cases_on_emulator(recyclable):
+    """every stop cause at every position with and without a First open, the
+    fragment-count sequences, and the empty and tiny logs
+    (walcases.stop_and_fragment_cases), every mode: records with their
+    fragment counts, reports, counts, n_physical, stop offset and stop reason
+    (the GPU twin is tests/test_gpu_contracts.py)"""
+    E = _emu()
+    for name, log, ln in W.stop_and_fragment_cases(recyclable):
         for mode in MODES:
             recs, reps, res = E.wal_recover(log, ln, mode)
             compare(recs, reps, res, log, ln, mode, name)

@@ -380,3 +380,179 @@ def long_control_runs(recyclable, run=200, seed=41):
     set_type(buf, int(po[k + run]), 2 + base)     # over the run: rw_emit's capped walk)
     set_type(buf, int(po[k + run + 1]), 4 + base)
     return [("long_ctl", buf, ln)]
+
+
+# ---- stop causes, fragment counts and tiny logs, built record by record -----
+
+class _Log:
+    """a log written one physical record at a time, the writer's block rule
+    kept (a block tail shorter than the header is zero-filled,
+    log_writer.cc:91-100), so every header is one the reader's chain reaches"""
+
+    def __init__(self, recyclable, log_number=7, seed=1):
+        self.rec, self.ln = recyclable, log_number
+        self.buf = bytearray()
+        self.rng = np.random.default_rng(seed)
+
+    def data(self, n):
+        return self.rng.integers(0, 256, n, np.uint8).tobytes()
+
+    def put(self, t, payload=b"", log_number=None):
+        """t in 1..4: Full / First / Middle / Last in this log's header kind;
+        any other value is the type byte itself (9 always has the 7-byte
+        header, 11 the 11-byte one, log_writer.cc:228-263)"""
+        if isinstance(payload, int):
+            payload = self.data(payload)
+        if 1 <= t <= 4 and self.rec:
+            t += 4
+        hs = 11 if (5 <= t <= 8 or t == 11) else 7
+        o = len(self.buf) % BLOCK
+        if BLOCK - o < hs:
+            self.buf += bytes(BLOCK - o)
+            o = 0
+        assert o + hs + len(payload) <= BLOCK
+        h = bytearray(hs)
+        h[4:6] = struct.pack("<H", len(payload))
+        h[6] = t
+        if hs == 11:
+            h[7:11] = struct.pack("<I", self.ln if log_number is None else log_number)
+        h[0:4] = struct.pack("<I", O.mask(O.crc32c_value(bytes(h[6:]) + payload)))
+        at = len(self.buf)
+        self.buf += h + payload
+        return at
+
+    def goto(self, target):
+        """Full records up to block offset `target` (of this block or the next)"""
+        hs = 11 if self.rec else 7
+        while len(self.buf) % BLOCK != target:
+            o = len(self.buf) % BLOCK
+            if target >= o + hs:
+                self.put(1, target - o - hs)
+            elif BLOCK - o < hs:
+                self.buf += bytes(BLOCK - o)
+            else:
+                self.put(1, BLOCK - o - hs)
+
+    def array(self):
+        return np.frombuffer(bytes(self.buf), np.uint8).copy()
+
+
+def stop_and_fragment_cases(recyclable):
+    """(name, log, log_number): small logs (<= 6 log blocks) for the outputs no
+    scenario above reaches.
+
+    Stop cases -- one cause of ReadRecord returning false per log, with no
+    fragment open and right behind a First ("+open": the "error reading
+    trailing data" paths), at the first byte of a block ("blk"), mid-block in
+    a full block ("mid"), in the short last block ("last") and as the very
+    first record ("first"): the log's end ("eof"), a truncated header ("hdr"),
+    a truncated body ("body"), and kEof in front of the log's end from a
+    record of the reader's own result type 12 ("p12"; types 14 and 16 are in
+    the fixture logs); on recyclable headers an old record ("old": reading
+    goes on in kSkipAnyCorruptedRecords) and, on the recycled log, a CRC and a
+    length fault ("crc", "len": the tolerated corrupt tail of mode 0, reports
+    in the others).  Every cause that does not need the log's end is followed
+    by good records.
+
+    Fragment-count cases ("frags", and "frags_x" with the same records laid
+    across a block boundary): First First Last; First(empty) Middle Last; an
+    empty record in one fragment and in three; five fragments; First control
+    Last and First control control Middle Last with each control type, one
+    control payload of exactly the Last's length; a fragmented record right
+    after an aborted one (its XXH3 covers the aborted fragments, its count
+    does not); a Middle and a Last with no start, then a good record.
+
+    Empty and tiny logs: 0, 1..6, 7 and 11 bytes of a log, and 100 zero bytes
+    (those under 7 bytes and the zeros with the legacy headers only: no type
+    byte of theirs is read, log_reader.cc:454-461)."""
+    ln = 7
+    hs = 11 if recyclable else 7
+    ts_type = 11 if recyclable else 10
+    out = []
+    eof_only = ("eof", "hdr", "body")
+    causes = [("eof", ("blk", "last")), ("hdr", ("blk", "last")),
+              ("body", ("blk", "last", "first")), ("p12", ("blk", "mid", "first"))]
+    if recyclable:
+        causes += [("crc", ("blk", "mid", "last", "first")), ("len", ("mid",)),
+                   ("old", ("blk", "mid", "last", "first"))]
+    for cause, places in causes:
+        for pos in places:
+            for open_ in (False, True):
+                if open_ and pos == "first":
+                    continue
+                b = _Log(recyclable, ln, seed=len(out) + 1)
+                lead = hs + 20 if open_ else 0  # the First in front of the cause
+                if pos != "first":
+                    b.put(1, 40)
+                if pos == "blk":
+                    b.goto((BLOCK - lead) % BLOCK)
+                elif pos == "mid":
+                    b.goto(9000)
+                elif pos == "last":
+                    b.goto(0)
+                    b.put(1, 5)
+                    b.goto(3000)
+                if open_:
+                    b.put(2, 20)
+                if cause == "hdr":
+                    b.buf += b.data(3)
+                elif cause == "body":
+                    at = b.put(1, 500)
+                    del b.buf[at + hs + 100:]
+                elif cause[0] == "p":
+                    b.put(int(cause[1:]), 30)
+                elif cause == "crc":
+                    b.buf[b.put(1, 30) + hs + 4] ^= 0x20
+                elif cause == "len":
+                    at = b.put(1, 30)
+                    b.buf[at + 4:at + 6] = b"\xff\xff"
+                elif cause == "old":
+                    b.put(1, 30, log_number=ln + 1)
+                if cause not in eof_only:  # reading would go on: good records behind it
+                    b.put(1, 10)
+                    b.put(2, 33)
+                    b.put(4, 44)
+                    if pos != "last":  # (a full block: its faults are not the log's end)
+                        b.goto(0)
+                        b.put(2, 12)
+                        b.put(4, 13)
+                        b.put(1, 77)
+                out.append((f"{cause}@{pos}" + ("+open" if open_ else ""), b.array(), ln))
+
+    def ts(*pairs):
+        return b"".join(struct.pack("<IH", cf, t) for cf, t in pairs)
+
+    for name, start in (("frags", 0), ("frags_x", BLOCK - 60)):
+        b = _Log(recyclable, ln, seed=77)
+        b.put(1, 10)
+        b.goto(start)
+        b.put(2, 8), b.put(2, 9), b.put(4, 10)              # First First Last
+        b.put(2, 0), b.put(3, 7), b.put(4, 3)               # First(empty) Middle Last
+        b.put(1, 0)                                         # empty, one fragment
+        b.put(2, 0), b.put(3, 0), b.put(4, 0)               # empty, three fragments
+        b.put(2, 5), b.put(3, 300), b.put(3, 0), b.put(3, 17), b.put(4, 6)  # five fragments
+        cf = 100
+        for c in (9, ts_type):
+            def ctl(n_pairs=1):
+                nonlocal cf
+                cf += n_pairs
+                return struct.pack("<I", 0) if c == 9 else \
+                    ts(*[(cf - k, 8) for k in range(n_pairs)])
+            b.put(2, 12), b.put(c, ctl()), b.put(4, 15)     # First control Last
+            b.put(2, 12), b.put(c, ctl()), b.put(c, ctl()), b.put(3, 9), b.put(4, 21)
+            p = ctl(2)                                       # ... the Last as long as the control
+            b.put(2, 12), b.put(c, p), b.put(4, len(p))
+        b.put(2, 30), b.put(3, 10), b.put(30, 4)            # aborted by an unknown type ...
+        b.put(2, 5), b.put(4, 6)                            # ... its XXH3 state still fed
+        b.put(3, 9), b.put(4, 9), b.put(1, 20)              # no start, no start, good
+        b.put(2, 4000), b.put(3, 2), b.put(4, 1)
+        out.append((name, b.array(), ln))
+
+    one = _Log(recyclable, ln, seed=5)
+    one.put(1, 20)
+    whole = one.array()
+    for n in (7, 11) if recyclable else (0, 1, 2, 3, 4, 5, 6, 7, 11):
+        out.append((f"len{n}", whole[:n].copy(), ln))
+    if not recyclable:
+        out.append(("zeros", np.zeros(100, np.uint8), ln))
+    return out
