@@ -115,6 +115,12 @@ def lib():
         "forst_trailer_writer_close": (i, [vp]),
         "forst_trailer_writer_last_error": (ctypes.c_char_p, []),
         "forst_sst_footer_build": (i, [u32, i, u64, u32, u64, u64, u64, u64, vp, vp, vp]),
+        "forst_blob_verify_batch": (i, [vp, u64, vp, vp, vp, vp, u64, vp, vp, vp, vp, vp, u64,
+                                        vp]),
+        "forst_blob_record_crc_batch": (i, [vp, u64, vp, vp, vp, vp, u64, vp]),
+        "forst_blob_file_reason_text": (ctypes.c_char_p, [i]),
+        "forst_blob_walk_file": (i, [vp, u64, vp, vp, u64, vp, vp, vp]),
+        "forst_blob_verify_files": (i, [vp, vp, vp, vp, u64, vp, u64, vp, vp]),
         "forst_wal_recover_batch": None,  # struct arguments: argtypes set by engine
     }
     for name, sig in sigs.items():

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/forst_checksum.h"
+#include "blob_host.h"
 #include "engine.h"
 
 #define FORST_API extern "C" __attribute__((visibility("default")))
@@ -534,6 +535,156 @@ FORST_API int forst_wal_record_crc_lengths(uint8_t* log, uint64_t log_len,
   a.crc_out = crc_out;
   return hip_status(launch_wal_record_crc(a, static_cast<hipStream_t>(stream), &g_last_kernel),
                     "wal_record_crc_lengths launch");
+}
+
+// ---- blob file records (blob.h, blob_host.h) ---------------------------------
+
+FORST_API int forst_blob_verify_batch(const uint8_t* base, uint64_t base_len,
+                                      const uint64_t* record_offsets,
+                                      const uint64_t* expect_key_sizes,
+                                      const uint64_t* expect_value_sizes, const uint8_t* user_keys,
+                                      uint64_t user_keys_len, const uint64_t* user_key_offsets,
+                                      uint8_t* status, uint32_t* header_crc, uint32_t* blob_crc,
+                                      unsigned long long* mismatches, uint64_t n_records,
+                                      void* stream) {
+  if (n_records == 0) return FORST_OK;
+  if (!record_offsets || !status)
+    return set_error(FORST_EINVAL, "record_offsets/status must be non-null");
+  if (base_len && (!base || !aligned4(base)))
+    return set_error(FORST_EINVAL, "base must be non-null, 4-byte aligned");
+  if ((user_keys != nullptr) != (user_key_offsets != nullptr))
+    return set_error(FORST_EINVAL, "user_keys and user_key_offsets go together");
+  if (user_key_offsets && !expect_key_sizes)
+    return set_error(FORST_EINVAL, "user keys need expect_key_sizes (their lengths)");
+  int rc = check_device();
+  if (rc) return rc;
+  BlobArgs a{};
+  a.base = base;
+  a.base_len = base_len;
+  a.record_offsets = record_offsets;
+  a.expect_key_sizes = expect_key_sizes;
+  a.expect_value_sizes = expect_value_sizes;
+  a.user_keys = user_keys;
+  a.user_keys_len = user_keys_len;
+  a.user_key_offsets = user_key_offsets;
+  a.status = status;
+  a.header_crc = header_crc;
+  a.blob_crc = blob_crc;
+  a.mismatches = mismatches;
+  a.n = n_records;
+  return hip_status(launch_blob_records(a, static_cast<hipStream_t>(stream), &g_last_kernel),
+                    "blob_verify launch");
+}
+
+FORST_API int forst_blob_record_crc_batch(uint8_t* base, uint64_t base_len,
+                                          const uint64_t* record_offsets, uint8_t* status,
+                                          uint32_t* header_crc, uint32_t* blob_crc,
+                                          uint64_t n_records, void* stream) {
+  if (n_records == 0) return FORST_OK;
+  if (!record_offsets || !status)
+    return set_error(FORST_EINVAL, "record_offsets/status must be non-null");
+  if (base_len && (!base || !aligned4(base)))
+    return set_error(FORST_EINVAL, "base must be non-null, 4-byte aligned");
+  int rc = check_device();
+  if (rc) return rc;
+  BlobArgs a{};
+  a.base = base;
+  a.base_w = base;
+  a.base_len = base_len;
+  a.record_offsets = record_offsets;
+  a.status = status;
+  a.header_crc = header_crc;
+  a.blob_crc = blob_crc;
+  a.n = n_records;
+  a.write = 1;
+  return hip_status(launch_blob_records(a, static_cast<hipStream_t>(stream), &g_last_kernel),
+                    "blob_record_crc launch");
+}
+
+FORST_API const char* forst_blob_file_reason_text(int reason) {
+  return blobhost::reason_text(reason);
+}
+
+FORST_API int forst_blob_verify_files(const uint8_t* const* host_files, const uint64_t* file_sizes,
+                                      const uint64_t* dev_offsets, const uint8_t* dev_arena,
+                                      uint64_t arena_len, const uint32_t* expect_cf_ids,
+                                      uint64_t n_files, forst_blob_file_result* out,
+                                      void* stream) {
+  if (n_files == 0) return FORST_OK;
+  if (!host_files || !file_sizes || !dev_offsets || !out)
+    return set_error(FORST_EINVAL, "host_files/file_sizes/dev_offsets/out must be non-null");
+  if (n_files > (uint64_t(1) << 32)) return set_error(FORST_EINVAL, "n_files too large");
+  for (uint64_t f = 0; f < n_files; ++f) {
+    if (file_sizes[f] && !host_files[f])
+      return set_error(FORST_EINVAL, "host_files[" + std::to_string(f) + "] must be non-null");
+    if (dev_offsets[f] > arena_len || file_sizes[f] > arena_len - dev_offsets[f])
+      return set_error(FORST_EINVAL, "file " + std::to_string(f) + " [" +
+                                         std::to_string(dev_offsets[f]) + ", +" +
+                                         std::to_string(file_sizes[f]) + ") outside the arena of " +
+                                         std::to_string(arena_len) + " bytes");
+  }
+  // the host walk: per file, the record offsets (file-relative) and whether
+  // its CRCs are still to be checked
+  std::vector<blobhost::Walk> walks(n_files);
+  std::vector<uint64_t> rec_off, first(n_files + 1, 0), dev_off, foot_file;
+  for (uint64_t f = 0; f < n_files; ++f) {
+    first[f] = rec_off.size();
+    walks[f] = blobhost::walk_file(host_files[f], file_sizes[f],
+                                   expect_cf_ids ? expect_cf_ids + f : nullptr, out + f,
+                                   [&](uint64_t off) { rec_off.push_back(off); });
+    if (out[f].reason != FORST_BLOB_FILE_OK) {
+      rec_off.resize(first[f]);  // decided on the host: nothing of it is launched
+      continue;
+    }
+    foot_file.push_back(f);
+  }
+  first[n_files] = rec_off.size();
+  if (foot_file.empty()) return FORST_OK;  // every file decided on the host
+  if (!dev_arena || !aligned4(dev_arena))
+    return set_error(FORST_EINVAL, "dev_arena must be non-null, 4-byte aligned");
+  int rc = check_device();
+  if (rc) return rc;
+  const uint64_t n = rec_off.size(), nf = foot_file.size(), total = n + nf;
+  dev_off.resize(total);
+  for (uint64_t f = 0; f < n_files; ++f)
+    for (uint64_t k = first[f]; k < first[f + 1]; ++k) dev_off[k] = dev_offsets[f] + rec_off[k];
+  for (uint64_t j = 0; j < nf; ++j)
+    dev_off[n + j] = dev_offsets[foot_file[j]] + file_sizes[foot_file[j]] - blobhost::kFooter;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t off_bytes = (8 * total + 255) & ~size_t(255);
+  void* scratch = nullptr;
+  hipError_t e = scratch_alloc(&scratch, off_bytes + total, s);
+  if (e != hipSuccess) return hip_status(e, "blob_verify_files scratch");
+  uint64_t* d_off = static_cast<uint64_t*>(scratch);
+  uint8_t* d_st = static_cast<uint8_t*>(scratch) + off_bytes;
+  std::vector<uint8_t> st(total);
+  // pageable vectors on both ends: each copy is followed by a stream
+  // synchronisation while the vector is alive
+  if ((e = hipMemcpyAsync(d_off, dev_off.data(), 8 * total, hipMemcpyHostToDevice, s)) ==
+          hipSuccess &&
+      (e = hipStreamSynchronize(s)) == hipSuccess) {
+    BlobArgs a{};
+    a.base = dev_arena;
+    a.base_len = arena_len;
+    a.record_offsets = d_off;
+    a.footer_offsets = d_off + n;
+    a.n = n;
+    a.n_footers = nf;
+    a.status = d_st;
+    e = launch_blob_records(a, s, &g_last_kernel);
+    if (e == hipSuccess) e = hipMemcpyAsync(st.data(), d_st, total, hipMemcpyDeviceToHost, s);
+    const hipError_t se = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = se;
+  }
+  const hipError_t fr = scratch_free(scratch, s);
+  if (e == hipSuccess) e = fr;
+  if (e != hipSuccess) return hip_status(e, "blob_verify_files launch");
+  for (uint64_t j = 0; j < nf; ++j) {
+    const uint64_t f = foot_file[j];
+    blobhost::resolve_file(walks[f], rec_off.data() + first[f], st.data() + first[f], st[n + j],
+                           out + f);
+  }
+  return FORST_OK;
 }
 
 namespace forst {

@@ -133,6 +133,33 @@ struct WalArgs {
   int recyclable;
 };
 
+// Blob file records (blob.h, compiled into wal.hip): verify (write = 0,
+// BlobFileReader::VerifyBlob) or fill both CRC fields in place (write = 1,
+// BlobLogRecord::EncodeHeaderTo).  Status codes: FORST_BLOB_* (forst_checksum.h).
+struct BlobArgs {
+  const uint8_t* base;
+  uint8_t* base_w;  // write mode
+  uint64_t base_len;
+  const uint64_t* record_offsets;      // header of record i, any order
+  const uint64_t* expect_key_sizes;    // verify, nullable
+  const uint64_t* expect_value_sizes;  // verify, nullable
+  const uint8_t* user_keys;            // verify, nullable (needs expect_key_sizes)
+  uint64_t user_keys_len;
+  const uint64_t* user_key_offsets;
+  uint8_t* status;                 // n + n_footers
+  uint32_t* header_crc;            // nullable, n
+  uint32_t* blob_crc;              // nullable, n
+  unsigned long long* mismatches;  // nullable
+  uint64_t n;
+  int write;
+  // file scans (forst_blob_verify_files): BlobLogFooters whose CRC
+  // (footer[0..28) vs the masked LE32 behind it, blob_log_format.cc:72-94)
+  // rides in the same batch; footer j's status (0, 5 or 6) at status[n + j]
+  const uint64_t* footer_offsets;  // nullable
+  uint64_t n_footers;
+};
+hipError_t launch_blob_records(const BlobArgs& a, hipStream_t stream, const char** kernel_name);
+
 // Per-KV protection / Hash64 batches (kv_protect.hip).
 enum KvMode : int {
   kKvHash = 0,     // out[i] = Hash64(key_i, seeds ? seeds[i] : seed)

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <chrono>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -171,6 +172,150 @@ Status BlockChecksumEngine::VerifyBlocks(ChecksumType type, uint32_t base_contex
     }
   }
   return first;
+}
+
+// ---- blob files ----------------------------------------------------------------
+
+BlobRecords::~BlobRecords() { (void)hipFree(dev_); }
+
+uint8_t* BlobRecords::Grow(uint64_t bytes, Status* s) {
+  if (bytes > cap_) {
+    (void)hipFree(dev_);
+    dev_ = nullptr;
+    cap_ = 0;
+    *s = FromHip(hipMalloc(&dev_, bytes), "hipMalloc");
+    if (!s->ok()) return nullptr;
+    cap_ = bytes;
+  }
+  return static_cast<uint8_t*>(dev_);
+}
+
+bool BlobRecords::IsValidBlobOffset(uint64_t value_offset, uint64_t key_size, uint64_t value_size,
+                                    uint64_t file_size) {
+  // BlobLogHeader::kSize 30, BlobLogRecord::kHeaderSize 32, BlobLogFooter::kSize 32
+  if (value_offset < 30 + 32 + key_size) return false;
+  if (value_offset + value_size + 32 > file_size) return false;
+  return true;
+}
+
+Status BlobRecords::RecordStatus(uint8_t code) {
+  switch (code) {
+    case FORST_BLOB_OK:
+      return Status::OK();
+    case FORST_BLOB_HEADER_CRC:
+      return Status::Corruption("Error while decoding blob record: Header CRC mismatch");
+    case FORST_BLOB_KEY_SIZE:
+      return Status::Corruption("Key size mismatch when reading blob");
+    case FORST_BLOB_VALUE_SIZE:
+      return Status::Corruption("Value size mismatch when reading blob");
+    case FORST_BLOB_KEY:
+      return Status::Corruption("Key mismatch when reading blob");
+    case FORST_BLOB_CRC:
+      return Status::Corruption("Blob CRC mismatch");
+    case FORST_BLOB_OUT_OF_RANGE:
+      return Status::InvalidArgument("blob record outside the device buffer");
+    case FORST_BLOB_TOO_LARGE:
+      return Status::InvalidArgument("blob record larger than 4 GiB");
+  }
+  return Status::InvalidArgument("unknown blob record status " + std::to_string(code));
+}
+
+Status BlobRecords::FileStatus(const forst_blob_file_result& r) {
+  if (r.reason == FORST_BLOB_FILE_OK) return Status::OK();
+  const std::string text = forst_blob_file_reason_text(r.reason);  // "Corruption: <message>"
+  return Status::Corruption(text.substr(text.find(": ") + 2));
+}
+
+Status BlobRecords::VerifyRecords(const uint8_t* dev_file, uint64_t file_size,
+                                  const std::vector<BlobRequest>& requests,
+                                  std::vector<Status>* statuses) {
+  const uint64_t n = requests.size();
+  statuses->assign(n, Status::OK());
+  if (!n) return Status::OK();
+  // one host image of the request arrays: record offsets, key sizes, value
+  // sizes, user key offsets (u64 x n each), then the user keys
+  uint64_t key_bytes = 0;
+  for (const BlobRequest& r : requests) key_bytes += r.user_key_size;
+  const uint64_t keys_at = 32 * n, status_at = (keys_at + key_bytes + 7) & ~uint64_t(7);
+  std::vector<uint8_t> img(status_at + n);
+  uint64_t* off = reinterpret_cast<uint64_t*>(img.data());
+  uint64_t *eks = off + n, *evs = off + 2 * n, *uko = off + 3 * n;
+  uint64_t kpos = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    const BlobRequest& r = requests[i];
+    const bool valid = IsValidBlobOffset(r.offset, r.user_key_size, r.value_size, file_size);
+    // BlobIndex offset - BlobLogRecord::CalculateAdjustmentForRecordHeader(key_size)
+    off[i] = valid ? r.offset - (r.user_key_size + 32) : UINT64_MAX;
+    eks[i] = r.user_key_size;
+    evs[i] = r.value_size;
+    uko[i] = kpos;
+    if (r.user_key_size) std::memcpy(img.data() + keys_at + kpos, r.user_key, r.user_key_size);
+    kpos += r.user_key_size;
+    if (!valid) (*statuses)[i] = Status::Corruption("Invalid blob offset");
+  }
+  Status s;
+  uint8_t* d = Grow(img.size(), &s);
+  if (!d) return s;
+  hipStream_t st = static_cast<hipStream_t>(stream_);
+  // blocking copies: the pageable image is read before hipMemcpy returns
+  s = FromHip(hipMemcpy(d, img.data(), status_at, hipMemcpyHostToDevice), "hipMemcpy");
+  if (!s.ok()) return s;
+  const uint64_t* d64 = reinterpret_cast<const uint64_t*>(d);
+  s = FromRc(forst_blob_verify_batch(dev_file, file_size, d64, d64 + n, d64 + 2 * n, d + keys_at,
+                                     key_bytes, d64 + 3 * n, d + status_at, nullptr, nullptr,
+                                     nullptr, n, stream_));
+  if (s.ok()) s = FromHip(hipStreamSynchronize(st), "hipStreamSynchronize");
+  if (s.ok())
+    s = FromHip(hipMemcpy(img.data() + status_at, d + status_at, n, hipMemcpyDeviceToHost),
+                "hipMemcpy");
+  if (!s.ok()) return s;
+  for (uint64_t i = 0; i < n; ++i)
+    if ((*statuses)[i].ok()) (*statuses)[i] = RecordStatus(img[status_at + i]);
+  return Status::OK();
+}
+
+Status BlobRecords::FillRecordCrcs(uint8_t* dev_image, uint64_t image_len,
+                                   const std::vector<uint64_t>& record_offsets,
+                                   std::vector<uint8_t>* status) {
+  const uint64_t n = record_offsets.size();
+  if (status) status->assign(n, 0);
+  if (!n) return Status::OK();
+  Status s;
+  uint8_t* d = Grow(9 * n, &s);
+  if (!d) return s;
+  s = FromHip(hipMemcpy(d, record_offsets.data(), 8 * n, hipMemcpyHostToDevice), "hipMemcpy");
+  if (!s.ok()) return s;
+  s = FromRc(forst_blob_record_crc_batch(dev_image, image_len, reinterpret_cast<uint64_t*>(d),
+                                         d + 8 * n, nullptr, nullptr, n, stream_));
+  if (s.ok())
+    s = FromHip(hipStreamSynchronize(static_cast<hipStream_t>(stream_)), "hipStreamSynchronize");
+  if (s.ok() && status)
+    s = FromHip(hipMemcpy(status->data(), d + 8 * n, n, hipMemcpyDeviceToHost), "hipMemcpy");
+  return s;
+}
+
+std::vector<Status> BlobRecords::VerifyFiles(const std::vector<BlobFileRef>& files,
+                                             const uint8_t* dev_arena, uint64_t arena_len,
+                                             std::vector<forst_blob_file_result>* results) {
+  const uint64_t n = files.size();
+  std::vector<const uint8_t*> host(n);
+  std::vector<uint64_t> sizes(n), offs(n);
+  std::vector<uint32_t> cfs(n);
+  for (uint64_t i = 0; i < n; ++i) {
+    host[i] = files[i].host_file;
+    sizes[i] = files[i].file_size;
+    offs[i] = files[i].dev_offset;
+    cfs[i] = files[i].column_family_id;
+  }
+  std::vector<forst_blob_file_result> res(n);
+  const Status call = FromRc(forst_blob_verify_files(host.data(), sizes.data(), offs.data(),
+                                                     dev_arena, arena_len, cfs.data(), n,
+                                                     res.data(), stream_));
+  std::vector<Status> out(n, call);
+  if (call.ok())
+    for (uint64_t i = 0; i < n; ++i) out[i] = FileStatus(res[i]);
+  if (results) *results = std::move(res);
+  return out;
 }
 
 }  // namespace forst_gpu

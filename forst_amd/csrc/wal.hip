@@ -538,3 +538,6 @@ hipError_t launch_wal_record_xxh3(const WalArgs& a, uint64_t* out, uint64_t* out
 }
 
 }  // namespace forst
+
+// blob file records: the other CRC32C record format (launch_blob_records)
+#include "blob.h"

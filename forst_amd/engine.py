@@ -572,3 +572,102 @@ def fill_stream(dev_u8, start, seed, stream=None):
     check(lib().forst_fill_stream(dev_u8.data_ptr(), start, dev_u8.numel(), seed,
                                   _stream(stream)))
     return dev_u8
+
+
+# ---- blob file records (db/blob/blob_log_format.h) ----------------------------
+
+class BlobStatus(enum.IntEnum):
+    """per-record outcome of blob_verify_batch / blob_record_crc_batch
+    (FORST_BLOB_* in include/forst_checksum.h)"""
+    OK = 0
+    HEADER_CRC = 1
+    KEY_SIZE = 2
+    VALUE_SIZE = 3
+    KEY = 4
+    CRC = 5
+    OUT_OF_RANGE = 6
+    TOO_LARGE = 7
+
+
+_U64 = (torch.int64, torch.uint64)
+_U32 = (torch.int32, torch.uint32)
+
+
+def _arr(t, what, dtypes, dev, n=None):
+    """a device array handed to the engine: tensor, device, dtype, contiguity
+    and (n given) at least n elements"""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{what} must be a torch tensor")
+    if not t.is_cuda or t.device != dev:
+        raise ValueError(f"{what} must live on {dev}, not {t.device}")
+    if t.dtype not in dtypes:
+        raise ValueError(f"{what} must have dtype {' or '.join(str(d) for d in dtypes)}, "
+                         f"not {t.dtype}")
+    if not t.is_contiguous():
+        raise ValueError(f"{what} must be contiguous")
+    if n is not None and t.numel() < n:
+        raise ValueError(f"{what} holds {t.numel()} elements, {n} needed")
+    return t
+
+
+def _blob_out(t, what, dtype, dev, n):
+    """an optional result array: True = allocate, None / False = not wanted"""
+    if t is True:
+        return torch.empty(n, dtype=dtype, device=dev)
+    if t is None or t is False:
+        return None
+    return _arr(t, what, (dtype,) if dtype == torch.uint8 else _U32, dev, n)
+
+
+def blob_verify_batch(base, record_offsets, expect_key_sizes=None, expect_value_sizes=None,
+                      user_keys=None, user_key_offsets=None, status=True, header_crc=True,
+                      blob_crc=True, mismatches=None, stream=None):
+    """BlobFileReader::VerifyBlob per record (db/blob/blob_file_reader.cc:537-579)
+    over blob files resident on the device: record_offsets[i] = the start of
+    record i's 32-byte header, in any order.  expect_* / user keys (one uint8
+    buffer + per-record offsets, lengths = expect_key_sizes) are optional.
+    Returns (status, header_crc, blob_crc, mismatches); BlobStatus codes."""
+    _dev_u8(base)
+    dev = base.device
+    n = _arr(record_offsets, "record_offsets", _U64, dev).numel()
+    for t, what in ((expect_key_sizes, "expect_key_sizes"),
+                    (expect_value_sizes, "expect_value_sizes"),
+                    (user_key_offsets, "user_key_offsets")):
+        if t is not None:
+            _arr(t, what, _U64, dev, n)
+    if (user_keys is None) != (user_key_offsets is None):
+        raise ValueError("user_keys and user_key_offsets go together")
+    if user_keys is not None:
+        _arr(user_keys, "user_keys", (torch.uint8,), dev)
+        if expect_key_sizes is None:
+            raise ValueError("user keys need expect_key_sizes (their lengths)")
+    st = _blob_out(True if status is None else status, "status", torch.uint8, dev, n)
+    hc = _blob_out(header_crc, "header_crc", torch.uint32, dev, n)
+    bc = _blob_out(blob_crc, "blob_crc", torch.uint32, dev, n)
+    if mismatches is None:
+        mismatches = torch.zeros(1, dtype=torch.int64, device=dev)
+    else:
+        _arr(mismatches, "mismatches", _U64, dev, 1)
+    check(lib().forst_blob_verify_batch(
+        base.data_ptr(), base.numel(), record_offsets.data_ptr(), _p(expect_key_sizes),
+        _p(expect_value_sizes), _p(user_keys), 0 if user_keys is None else user_keys.numel(),
+        _p(user_key_offsets), st.data_ptr(), _p(hc), _p(bc), mismatches.data_ptr(), n,
+        _stream(stream)))
+    return st, hc, bc, mismatches
+
+
+def blob_record_crc_batch(base, record_offsets, status=True, header_crc=True, blob_crc=True,
+                          stream=None):
+    """BlobLogRecord::EncodeHeaderTo per record (db/blob/blob_log_format.cc:96-110)
+    for records laid out in a device image: fills header_crc and blob_crc in
+    place.  Returns (status, header_crc, blob_crc)."""
+    _dev_u8(base)
+    dev = base.device
+    n = _arr(record_offsets, "record_offsets", _U64, dev).numel()
+    st = _blob_out(True if status is None else status, "status", torch.uint8, dev, n)
+    hc = _blob_out(header_crc, "header_crc", torch.uint32, dev, n)
+    bc = _blob_out(blob_crc, "blob_crc", torch.uint32, dev, n)
+    check(lib().forst_blob_record_crc_batch(base.data_ptr(), base.numel(),
+                                            record_offsets.data_ptr(), st.data_ptr(), _p(hc),
+                                            _p(bc), n, _stream(stream)))
+    return st, hc, bc

@@ -425,4 +425,74 @@ class KvProtection {
   Status grow_status_;
 };
 
+// ---- Blob files ----------------------------------------
+//
+//   reference (per blob, CPU)                          this shim (per batch, GPU)
+//   BlobFileReader::VerifyBlob in GetBlob / MultiGetBlob BlobRecords::VerifyRecords
+//     (db/blob/blob_file_reader.cc:296-371, :390-535, :537-579)
+//   BlobLogRecord::EncodeHeaderTo in BlobLogWriter::AddRecord
+//     (db/blob/blob_log_format.cc:96-110)              BlobRecords::FillRecordCrcs
+//   BlobFileReader::Create + BlobLogSequentialReader::ReadRecord
+//     (blob_file_reader.cc:28-235,
+//      blob_log_sequential_reader.cc:64-114)           BlobRecords::VerifyFiles
+//
+// A request in the call site's vocabulary (BlobReadRequest,
+// db/blob/blob_read_request.h): the user key, and the BlobIndex's offset (of
+// the blob VALUE in the file) and size.
+struct BlobRequest {
+  const char* user_key = nullptr;
+  size_t user_key_size = 0;
+  uint64_t offset = 0;      // BlobIndex::offset()
+  uint64_t value_size = 0;  // BlobIndex::size()
+};
+// A blob file staged in a device arena (VerifyFiles): the file in host memory
+// and its bytes at dev_arena + dev_offset.
+struct BlobFileRef {
+  const uint8_t* host_file = nullptr;
+  uint64_t file_size = 0;
+  uint64_t dev_offset = 0;
+  uint32_t column_family_id = 0;  // BlobFileReader::Create's column_family_id
+};
+class BlobRecords {
+ public:
+  explicit BlobRecords(void* hip_stream = nullptr) : stream_(hip_stream) {}
+  ~BlobRecords();
+  BlobRecords(const BlobRecords&) = delete;
+  BlobRecords& operator=(const BlobRecords&) = delete;
+  // MultiGetBlob's verify loop over ONE blob file whose bytes lie at
+  // dev_file[0 .. file_size): statuses[i] is what GetBlob returns for request
+  // i up to and including VerifyBlob -- "Invalid blob offset" (IsValidBlobOffset,
+  // applied here on the host), then VerifyBlob's Corruption texts.  Requests in
+  // any order.  The request arrays are staged with blocking copies.
+  // Synchronises the stream.  The returned Status is OK unless the call itself
+  // failed.
+  Status VerifyRecords(const uint8_t* dev_file, uint64_t file_size,
+                       const std::vector<BlobRequest>& requests, std::vector<Status>* statuses);
+  // BlobLogWriter::EmitPhysicalRecord with the CRCs deferred: the records of a
+  // device image (headers with sizes and expiration, keys, values) get both
+  // CRC fields in place.  record_offsets: host.  status (optional): 0,
+  // FORST_BLOB_OUT_OF_RANGE or FORST_BLOB_TOO_LARGE per record.  Synchronises.
+  Status FillRecordCrcs(uint8_t* dev_image, uint64_t image_len,
+                        const std::vector<uint64_t>& record_offsets,
+                        std::vector<uint8_t>* status = nullptr);
+  // One Status per file: BlobFileReader::Create's, then the first failing
+  // record's (forst_blob_verify_files).  results (optional): the full results.
+  std::vector<Status> VerifyFiles(const std::vector<BlobFileRef>& files, const uint8_t* dev_arena,
+                                  uint64_t arena_len,
+                                  std::vector<forst_blob_file_result>* results = nullptr);
+  // the reference's Status of a FORST_BLOB_* code (InvalidArgument for the
+  // two without a reference twin, 6 and 7) and of a file result
+  static Status RecordStatus(uint8_t code);
+  static Status FileStatus(const forst_blob_file_result& r);
+  // db/blob/blob_log_format.h:150-162
+  static bool IsValidBlobOffset(uint64_t value_offset, uint64_t key_size, uint64_t value_size,
+                                uint64_t file_size);
+
+ private:
+  uint8_t* Grow(uint64_t bytes, Status* s);
+  void* stream_;
+  void* dev_ = nullptr;
+  uint64_t cap_ = 0;
+};
+
 }  // namespace forst_gpu

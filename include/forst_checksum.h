@@ -50,6 +50,14 @@
  *                                  (db/memtable.cc:273-307)
  *   forst_memtable_protect_batch<- MemTable::UpdateEntryChecksum
  *                                  (db/memtable.cc:676-693)
+ *   forst_blob_verify_batch     <- BlobFileReader::VerifyBlob
+ *                                  (db/blob/blob_file_reader.cc:537-579) as
+ *                                  called by GetBlob / MultiGetBlob
+ *   forst_blob_record_crc_batch <- BlobLogRecord::EncodeHeaderTo
+ *                                  (db/blob/blob_log_format.cc:96-110)
+ *   forst_blob_verify_files     <- BlobFileReader::Create (:28-235) +
+ *                                  BlobLogSequentialReader::ReadRecord
+ *                                  (db/blob/blob_log_sequential_reader.cc:64-114)
  *
  * Conventions
  *  - All array/buffer pointers are DEVICE pointers (hipMalloc'd, or host
@@ -726,6 +734,127 @@ int forst_sst_verify_files(const uint8_t* const* host_files, const uint64_t* fil
                            const uint64_t* dev_offsets, const uint8_t* dev_arena,
                            uint64_t arena_len, const char* const* file_names, uint64_t n_files,
                            forst_sst_verify_result* out, void* stream);
+
+/* ---- Blob files (db/blob/blob_log_format.h) ---------------------------------
+ * A blob file is a 30-byte BlobLogHeader, records, and a 32-byte CRC'd
+ * BlobLogFooter.  A record is a 32-byte header
+ *   key_size u64 | value_size u64 | expiration u64 | header_crc u32 | blob_crc u32
+ * followed by key and value (blob_log_format.h:96-116), with
+ *   header_crc = Mask(Value(header[0..24)))
+ *   blob_crc   = Mask(Extend(Value(key), value)) = Mask(Value(key || value))
+ * (BlobLogRecord::EncodeHeaderTo, blob_log_format.cc:96-110).  Records start
+ * at any byte (the first one at byte 30).
+ *
+ * Per-record status.  The first check that applies wins, in this order:
+ * header out of range (6), header CRC (1), key size (2), value size (3), too
+ * large (7), payload out of range (6), key bytes (4), blob CRC (5). */
+#define FORST_BLOB_OK 0
+#define FORST_BLOB_HEADER_CRC 1   /* "Error while decoding blob record: Header CRC mismatch"
+                                     (BlobLogRecord::DecodeHeaderFrom, blob_log_format.cc:126) */
+#define FORST_BLOB_KEY_SIZE 2     /* "Key size mismatch when reading blob" (blob_file_reader.cc:553) */
+#define FORST_BLOB_VALUE_SIZE 3   /* "Value size mismatch when reading blob" (:557) */
+#define FORST_BLOB_KEY 4          /* "Key mismatch when reading blob" (:563); also a user key
+                                     that reaches past user_keys_len (reported, never read) */
+#define FORST_BLOB_CRC 5          /* "Blob CRC mismatch" (BlobLogRecord::CheckBlobCRC,
+                                     blob_log_format.cc:138) */
+#define FORST_BLOB_OUT_OF_RANGE 6 /* the header or the payload reaches past base_len: reported,
+                                     never read (no reference twin: the reference is handed an
+                                     exact slice) */
+#define FORST_BLOB_TOO_LARGE 7    /* key_size + value_size > 2^32 - 1, or the sum overflows (no
+                                     twin: a WriteBatch cannot hold such a value) */
+
+/* BlobFileReader::VerifyBlob (db/blob/blob_file_reader.cc:537-579), as called
+ * by GetBlob (:296-371) and MultiGetBlob (:390-535) with verify_checksums, over
+ * n records of blob files resident in HBM.
+ * record_offsets[i] = start of record i's 32-byte header (BlobIndex offset -
+ * BlobLogRecord::CalculateAdjustmentForRecordHeader(key_size)), in any order.
+ * Device arrays.  expect_key_sizes / expect_value_sizes nullable (a scan takes
+ * the sizes from the headers); user_keys + user_key_offsets nullable, need
+ * expect_key_sizes (user key i = user_keys[user_key_offsets[i] ..
+ * + expect_key_sizes[i])).  Outputs nullable except status: status[i] = a
+ * FORST_BLOB_* code; header_crc[i] = the masked CRC computed over header bytes
+ * 0..24 (0: header out of range); blob_crc[i] = the masked CRC computed over
+ * key || value (0: the payload was not hashed, i.e. a status other than 0, 4
+ * or 5); *mismatches += the records with a non-zero status.
+ * Asynchronous on stream. */
+int forst_blob_verify_batch(const uint8_t* base, uint64_t base_len,
+                            const uint64_t* record_offsets, const uint64_t* expect_key_sizes,
+                            const uint64_t* expect_value_sizes, const uint8_t* user_keys,
+                            uint64_t user_keys_len, const uint64_t* user_key_offsets,
+                            uint8_t* status, uint32_t* header_crc, uint32_t* blob_crc,
+                            unsigned long long* mismatches, uint64_t n_records, void* stream);
+
+/* BlobLogRecord::EncodeHeaderTo (blob_log_format.cc:96-110), as called by
+ * BlobLogWriter::AddRecord -> EmitPhysicalRecord (db/blob/blob_log_writer.cc),
+ * for records already laid out in a device image (sizes and expiration in
+ * header bytes 0..24, key and value behind): fills both CRC fields in place
+ * (LE32 at +24 and +28).  status[i] is 0, FORST_BLOB_OUT_OF_RANGE or
+ * FORST_BLOB_TOO_LARGE; nothing is written for a non-zero record.  header_crc /
+ * blob_crc (nullable) receive the stored values (0 for a non-zero record's
+ * blob_crc).  Asynchronous on stream. */
+int forst_blob_record_crc_batch(uint8_t* base, uint64_t base_len, const uint64_t* record_offsets,
+                                uint8_t* status, uint32_t* header_crc, uint32_t* blob_crc,
+                                uint64_t n_records, void* stream);
+
+/* Why a blob file failed forst_blob_verify_files (forst_blob_file_reason_text
+ * gives the Status message). */
+enum forst_blob_file_reason {
+  FORST_BLOB_FILE_OK = 0,
+  FORST_BLOB_FILE_MALFORMED = 1,         /* "Malformed blob file" (blob_file_reader.cc:109) */
+  FORST_BLOB_FILE_HEADER_MAGIC = 2,      /* BlobLogHeader::DecodeFrom (blob_log_format.cc:43) */
+  FORST_BLOB_FILE_HEADER_VERSION = 3,    /* (:46) */
+  FORST_BLOB_FILE_TTL = 4,               /* "Unexpected TTL blob file" (blob_file_reader.cc:180, :231) */
+  FORST_BLOB_FILE_CF_MISMATCH = 5,       /* "Column family ID mismatch" (:184) */
+  FORST_BLOB_FILE_FOOTER_MAGIC = 6,      /* BlobLogFooter::DecodeFrom (blob_log_format.cc:88) */
+  FORST_BLOB_FILE_FOOTER_CRC = 7,        /* (:91) */
+  FORST_BLOB_FILE_RECORD_HEADER_CRC = 8, /* BlobLogRecord::DecodeHeaderFrom (:126) */
+  FORST_BLOB_FILE_RECORD_BLOB_CRC = 9,   /* BlobLogRecord::CheckBlobCRC (:138) */
+  FORST_BLOB_FILE_RECORD_CROSSES_FOOTER = 10, /* no reference twin */
+  FORST_BLOB_FILE_BLOB_COUNT_MISMATCH = 11,   /* no reference twin */
+  FORST_BLOB_FILE_RECORD_TOO_LARGE = 12,      /* FORST_BLOB_TOO_LARGE in a file; no twin */
+};
+
+typedef struct forst_blob_file_result {
+  int32_t status;            /* the reference's Status::Code: 0 kOk, 2 kCorruption */
+  int32_t reason;            /* forst_blob_file_reason */
+  uint64_t fail_index;       /* first failing record in file order (UINT64_MAX: none) */
+  uint64_t fail_offset;      /* ... and its header's offset in the file */
+  uint64_t blob_count;       /* records walked (all of them when status is 0) */
+  uint64_t total_blob_bytes; /* their 32 + key_size + value_size */
+  uint32_t column_family_id; /* the decoded BlobLogHeader */
+  uint8_t compression;
+  uint8_t has_ttl;
+  uint8_t reserved[2];
+} forst_blob_file_result;
+
+/* Status::ToString() of a forst_blob_file_reason ("OK", "Corruption: ...") */
+const char* forst_blob_file_reason_text(int reason);
+
+/* Host utility (no GPU call): the structure walk of forst_blob_verify_files
+ * over one file.  Applies the checks that need no CRC (file size, header,
+ * footer magic and TTL) and lists the record header offsets from byte 30.
+ * out->reason is the host-decided failure, or FORST_BLOB_FILE_OK when only
+ * the CRCs are left to check.  record_offsets (nullable) receives up to
+ * capacity offsets, *n_records the number walked.  *tail_crosses = 1 when the
+ * walk stopped at a record whose header fits in front of the footer and
+ * whose payload does not (it is the last offset listed). */
+int forst_blob_walk_file(const uint8_t* file, uint64_t file_size, const uint32_t* expect_cf_id,
+                         uint64_t* record_offsets, uint64_t capacity, uint64_t* n_records,
+                         int* tail_crosses, forst_blob_file_result* out);
+
+/* BlobFileReader::Create's checks (blob_file_reader.cc:28-77: OpenFile's size
+ * check :108, ReadHeader :139-190, ReadFooter :192-235) and then every record
+ * as BlobLogSequentialReader::ReadRecord(kReadHeaderKeyBlob) checks it
+ * (db/blob/blob_log_sequential_reader.cc:64-114), for n_files files:
+ * host_files[i] in host memory (structure is walked there), the same bytes at
+ * dev_arena + dev_offsets[i].  All CRCs of ALL files (record headers, payloads,
+ * footers) in one verify batch.  expect_cf_ids nullable.  out[i]: the first
+ * failure in this order -- file size, header, footer (magic, CRC, TTL), the
+ * records in file order, the footer's blob_count.  Synchronous. */
+int forst_blob_verify_files(const uint8_t* const* host_files, const uint64_t* file_sizes,
+                            const uint64_t* dev_offsets, const uint8_t* dev_arena,
+                            uint64_t arena_len, const uint32_t* expect_cf_ids, uint64_t n_files,
+                            forst_blob_file_result* out, void* stream);
 
 #ifdef __cplusplus
 }
