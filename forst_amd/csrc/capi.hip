@@ -5,8 +5,9 @@
 // (hipMallocFromPoolAsync / hipFreeAsync).  The block, raw-hash, combine, KV
 // and WAL-writer entry points never copy to the host or synchronise, so they
 // can be captured into hipGraphs (cdna_hip_programming.md Guideline 9);
-// forst_wal_verify_batch, forst_wal_record_xxh3_batch and forst_wal_recover_batch
-// read a record count back (one stream synchronisation each) and cannot be.
+// forst_wal_verify_batch, forst_wal_record_xxh3_batch, forst_wal_recover_batch
+// and forst_wal_records_compact read a count back (at least one stream
+// synchronisation each) and cannot be.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -535,6 +536,51 @@ FORST_API int forst_wal_record_crc_lengths(uint8_t* log, uint64_t log_len,
   a.crc_out = crc_out;
   return hip_status(launch_wal_record_crc(a, static_cast<hipStream_t>(stream), &g_last_kernel),
                     "wal_record_crc_lengths launch");
+}
+
+FORST_API int forst_wal_records_compact(const uint8_t* log, uint64_t log_len,
+                                        const uint64_t* rec_offset, const uint64_t* rec_length,
+                                        const uint32_t* rec_n_fragments, uint64_t n_records,
+                                        uint8_t* arena, uint64_t arena_capacity,
+                                        uint64_t* rep_offsets, uint32_t* rep_sizes,
+                                        uint8_t* status, uint64_t* arena_bytes, void* stream) {
+  if (!arena_bytes) return set_error(FORST_EINVAL, "arena_bytes must be non-null");
+  *arena_bytes = 0;
+  if (n_records == 0) return FORST_OK;
+  if (!rec_offset || !rec_length || !rec_n_fragments)
+    return set_error(FORST_EINVAL, "rec_offset/rec_length/rec_n_fragments must be non-null");
+  if (log_len && (!log || !aligned4(log)))
+    return set_error(FORST_EINVAL, "log must be non-null, 4-byte aligned");
+  if (!arena && arena_capacity) return set_error(FORST_EINVAL, "arena must be non-null");
+  if (reinterpret_cast<uintptr_t>(arena) & 15)
+    return set_error(FORST_EINVAL, "arena must be 16-byte aligned");
+  if (arena && log_len && arena_capacity) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(arena), l0 = reinterpret_cast<uintptr_t>(log);
+    if (a0 < l0 + log_len && l0 < a0 + arena_capacity)
+      return set_error(FORST_EINVAL, "arena overlaps the log");
+  }
+  int rc = check_device();
+  if (rc) return rc;
+  WcArgs a{};
+  a.log = log;
+  a.log_len = log_len;
+  a.rec_offset = rec_offset;
+  a.rec_length = rec_length;
+  a.rec_nfrag = rec_n_fragments;
+  a.n = n_records;
+  a.arena = arena;
+  a.capacity = arena_capacity;
+  a.rep_offsets = rep_offsets;
+  a.rep_sizes = rep_sizes;
+  a.status = status;
+  uint64_t total = 0;
+  const hipError_t e = launch_wal_records_compact(a, static_cast<hipStream_t>(stream), &total,
+                                                  &g_last_kernel);
+  *arena_bytes = total;
+  if (e == hipErrorInvalidValue && total > arena_capacity)
+    return set_error(FORST_EINVAL, "arena_capacity " + std::to_string(arena_capacity) + " < " +
+                                       std::to_string(total) + " arena bytes");
+  return hip_status(e, "wal_records_compact");
 }
 
 // ---- blob file records (blob.h, blob_host.h) ---------------------------------

@@ -277,6 +277,25 @@ struct WbArgs {
 hipError_t launch_write_batch_protect(const WbArgs& a, hipStream_t st, uint64_t* total,
                                       const char** kernel_name);
 
+// forst_wal_records_compact (wal_compact.h, compiled into wal.hip)
+struct WcArgs {
+  const uint8_t* log;
+  uint64_t log_len;
+  const uint64_t* rec_offset;  // device, n
+  const uint64_t* rec_length;
+  const uint32_t* rec_nfrag;
+  uint64_t n;
+  uint8_t* arena;         // nullable: sizes, offsets and status only
+  uint64_t capacity;
+  uint64_t* rep_offsets;  // out, nullable
+  uint32_t* rep_sizes;    // out, nullable
+  uint8_t* status;        // out, nullable
+};
+// synchronous (reads the arena total back into *total); fails with
+// hipErrorInvalidValue when an arena is given and *total > a.capacity
+hipError_t launch_wal_records_compact(const WcArgs& a, hipStream_t st, uint64_t* total,
+                                      const char** kernel_name);
+
 struct DeviceInfo {
   int device;
   int num_cus;

@@ -541,3 +541,5 @@ hipError_t launch_wal_record_xxh3(const WalArgs& a, uint64_t* out, uint64_t* out
 
 // blob file records: the other CRC32C record format (launch_blob_records)
 #include "blob.h"
+// recovered records as contiguous reps (launch_wal_records_compact)
+#include "wal_compact.h"

@@ -62,7 +62,11 @@ std::string WalReport::Text() const {
   return "unknown report reason " + std::to_string(reason);
 }
 
-WalRecovery::~WalRecovery() { (void)hipFree(dev_); }
+WalRecovery::~WalRecovery() {
+  (void)hipFree(dev_);
+  (void)hipFree(reps_);
+  (void)hipFree(arena_);
+}
 
 Status WalRecovery::Grow(uint64_t rec_cap, uint64_t rep_cap) {
   if (rec_cap <= rec_cap_ && rep_cap <= rep_cap_ && dev_) return Status::OK();
@@ -144,7 +148,10 @@ Status WalRecovery::Recover(const uint8_t* d_log, const uint8_t* host_log, uint6
 // as ReadPhysicalRecord skips it), behind the control record (types 9-11) at
 // that position when one lay between the record's fragments.  Reports made
 // during this ReadRecord call lie before the end of its last fragment.
-bool WalRecovery::Next(WalRecord* r) {
+bool WalRecovery::Next(WalRecord* r) { return Step(r, true); }
+bool WalRecovery::NextMeta(WalRecord* r) { return Step(r, false); }
+
+bool WalRecovery::Step(WalRecord* r, bool join) {
   if (!status_.ok()) return false;
   if (next_rec_ >= off_.size()) {
     trailing_.assign(reports_.begin() + static_cast<std::ptrdiff_t>(next_rep_), reports_.end());
@@ -187,7 +194,7 @@ bool WalRecovery::Next(WalRecord* r) {
     const char* payload = reinterpret_cast<const char*>(host_ + p + hs);
     if (nf == 1)
       single = payload;
-    else
+    else if (join)
       scratch_.append(payload, n);
     got += n;
     p += hs + n;
@@ -198,7 +205,7 @@ bool WalRecovery::Next(WalRecord* r) {
         "): use log::Reader for this log");
     return false;
   }
-  r->data = nf == 1 ? single : scratch_.data();
+  r->data = !join ? nullptr : nf == 1 ? single : scratch_.data();
   r->size = static_cast<size_t>(got);
   r->offset = off_[k];
   r->checksum = hash_[k];
@@ -207,6 +214,65 @@ bool WalRecovery::Next(WalRecord* r) {
   while (next_rep_ < reports_.size() && reports_[next_rep_].offset < p)
     r->reports_before.push_back(reports_[next_rep_++]);
   return true;
+}
+
+// The device arrays of the last Recover (offset, length, n_fragments) go
+// straight into forst_wal_records_compact: a count-only call sizes the arena,
+// the second call fills it.
+Status WalRecovery::CompactRecords(const uint8_t* d_log, WalDeviceRecords* out) {
+  *out = WalDeviceRecords{};
+  if (!status_.ok()) return status_;
+  const uint64_t n = off_.size();
+  if (!n) return Status::OK();
+  if (len_ && !d_log) return Status::InvalidArgument("null log");
+  if (n > reps_cap_) {
+    (void)hipFree(reps_);
+    reps_ = nullptr;
+    reps_cap_ = 0;
+    Status s = FromHip(hipMalloc(&reps_, align8(n * 13)), "hipMalloc");
+    if (!s.ok()) return s;
+    reps_cap_ = n;
+  }
+  char* p = static_cast<char*>(dev_);
+  const uint64_t* d_off = reinterpret_cast<const uint64_t*>(p);
+  const uint64_t* d_len = reinterpret_cast<const uint64_t*>(p + 8 * rec_cap_);
+  const uint32_t* d_nf = reinterpret_cast<const uint32_t*>(p + 24 * rec_cap_);
+  char* q = static_cast<char*>(reps_);
+  uint64_t* r_off = reinterpret_cast<uint64_t*>(q);
+  uint32_t* r_size = reinterpret_cast<uint32_t*>(q + 8 * reps_cap_);
+  uint8_t* r_st = reinterpret_cast<uint8_t*>(q + 12 * reps_cap_);
+  uint64_t total = 0;
+  Status s;
+  // An arena kept from an earlier call that holds the bound log_len + 15 n
+  // needs no count-only call (the walk, the scan and the read-back once, not
+  // twice).  The arena stays at the largest size seen until the object goes.
+  const bool fits = arena_ && arena_cap_ >= len_ + 15 * n;
+  if (!fits) {
+    s = FromRc(forst_wal_records_compact(d_log, len_, d_off, d_len, d_nf, n, nullptr, 0, r_off,
+                                         r_size, r_st, &total, stream_));
+    if (!s.ok()) return s;
+  }
+  if (!fits && (total > arena_cap_ || !arena_)) {
+    (void)hipFree(arena_);
+    arena_ = nullptr;
+    arena_cap_ = 0;
+    s = FromHip(hipMalloc(&arena_, total ? total : 16), "hipMalloc");
+    if (!s.ok()) return s;
+    arena_cap_ = total ? total : 16;
+  }
+  s = FromRc(forst_wal_records_compact(d_log, len_, d_off, d_len, d_nf, n,
+                                       static_cast<uint8_t*>(arena_), arena_cap_, r_off, r_size,
+                                       r_st, &total, stream_));
+  if (!s.ok()) return s;
+  s = FromHip(hipStreamSynchronize(static_cast<hipStream_t>(stream_)), "hipStreamSynchronize");
+  if (!s.ok()) return s;
+  out->arena = static_cast<const uint8_t*>(arena_);
+  out->arena_bytes = total;
+  out->rep_offsets = r_off;
+  out->rep_sizes = r_size;
+  out->status = r_st;
+  out->n = n;
+  return Status::OK();
 }
 
 WalWriteGroup::~WalWriteGroup() { (void)hipFree(dev_); }
@@ -446,29 +512,48 @@ Status KvProtection::WriteBatchProtection(const std::vector<KvBytes>& reps,
   std::vector<uint32_t> sizes(n);
   for (uint64_t i = 0; i < n; ++i) sizes[i] = static_cast<uint32_t>(reps[i].size);
   void* aux = nullptr;
-  s = FromHip(hipMalloc(&aux, 8 * (2 * n + 1) + 4 * n + 4 * n + n + 64), "hipMalloc");
+  s = FromHip(hipMalloc(&aux, 8 * n + 4 * n), "hipMalloc");
   if (!s.ok()) return s;
   uint64_t* d_off = static_cast<uint64_t*>(aux);
-  uint64_t* d_first = d_off + n;
-  uint32_t* d_sz = reinterpret_cast<uint32_t*>(d_first + n + 1);
-  uint32_t* d_np = d_sz + n;
-  uint8_t* d_st = reinterpret_cast<uint8_t*>(d_np + n);
+  uint32_t* d_sz = reinterpret_cast<uint32_t*>(d_off + n);
   hipStream_t st = static_cast<hipStream_t>(stream_);
   s = FromHip(hipMemcpyAsync(d_off, offs.data(), 8 * n, hipMemcpyHostToDevice, st), "hipMemcpyAsync");
   if (s.ok()) s = FromHip(hipMemcpyAsync(d_sz, sizes.data(), 4 * n, hipMemcpyHostToDevice, st), "hipMemcpyAsync");
+  // (offs / sizes outlive the copies: the call below ends with a stream synchronisation)
+  if (s.ok())
+    s = WriteBatchProtectionDevice(static_cast<uint8_t*>(dev_), img, d_off, d_sz, n, prot,
+                                   rep_status);
+  (void)hipFree(aux);
+  return s;
+}
+
+Status KvProtection::WriteBatchProtectionDevice(const uint8_t* d_base, uint64_t base_len,
+                                                const uint64_t* d_off, const uint32_t* d_sz,
+                                                uint64_t n,
+                                                std::vector<std::vector<uint64_t>>* prot,
+                                                std::vector<Status>* rep_status) {
+  prot->assign(n, std::vector<uint64_t>());
+  rep_status->assign(n, Status::OK());
+  if (!n) return Status::OK();
+  void* aux = nullptr;
+  Status s = FromHip(hipMalloc(&aux, 8 * (n + 1) + 4 * n + n + 64), "hipMalloc");
+  if (!s.ok()) return s;
+  uint64_t* d_first = static_cast<uint64_t*>(aux);
+  uint32_t* d_np = reinterpret_cast<uint32_t*>(d_first + n + 1);
+  uint8_t* d_st = reinterpret_cast<uint8_t*>(d_np + n);
+  hipStream_t st = static_cast<hipStream_t>(stream_);
   uint64_t total = 0;
-  if (s.ok()) {
-    const int rc = forst_write_batch_protect_batch(static_cast<uint8_t*>(dev_), img, d_off, d_sz, n,
-                                                   d_first, nullptr, 0, nullptr, nullptr, &total,
-                                                   stream_);
+  {
+    const int rc = forst_write_batch_protect_batch(d_base, base_len, d_off, d_sz, n, d_first,
+                                                   nullptr, 0, nullptr, nullptr, &total, stream_);
     if (rc != FORST_OK && !(rc == FORST_EINVAL && total > 0)) s = FromRc(rc);
   }
   void* d_prot = nullptr;
   if (s.ok()) s = FromHip(hipMalloc(&d_prot, 8 * (total ? total : 1)), "hipMalloc");
   if (s.ok())
-    s = FromRc(forst_write_batch_protect_batch(static_cast<uint8_t*>(dev_), img, d_off, d_sz, n,
-                                               d_first, static_cast<uint64_t*>(d_prot), total,
-                                               d_st, d_np, &total, stream_));
+    s = FromRc(forst_write_batch_protect_batch(d_base, base_len, d_off, d_sz, n, d_first,
+                                               static_cast<uint64_t*>(d_prot), total, d_st, d_np,
+                                               &total, stream_));
   std::vector<uint64_t> first(n + 1, 0), all(total ? total : 1);
   std::vector<uint32_t> np(n);
   std::vector<uint8_t> code(n);

@@ -379,6 +379,47 @@ def wal_recover_batch(log, log_number=0, mode=kPointInTimeRecovery, record_capac
     return rec, rep, res
 
 
+def wal_records_compact(log, records, arena=None, stream=None):
+    """The bytes log::Reader::ReadRecord returns for each record, contiguous in
+    a device arena (forst_wal_records_compact): the reps
+    write_batch_protect_batch and xxh3_64_batch take.  records: the dict
+    wal_recover_batch returns (its offset / length / n_fragments members) or
+    the tuple (offset, length, hash, n_fragments); any subset or order of a
+    log's records.  Returns (arena, rep_offsets int64,
+    rep_sizes int32, status uint8): record i's bytes are
+    arena[rep_offsets[i]:rep_offsets[i] + rep_sizes[i]], every rep on a 16-byte
+    boundary with zero padding behind it, the arena cut to the bytes used.
+    arena: the caller's own uint8 tensor (16-byte aligned, apart from the log);
+    left out, it is sized by a first, count-only call.  An arena below the
+    total raises a ForstError whose arena_bytes is the size to call again with.
+    Synchronous (one read-back of the total per call)."""
+    _dev_u8(log)
+    if isinstance(records, dict):
+        off, length, nfrag = (records[k] for k in ("offset", "length", "n_fragments"))
+    else:  # (offset, length, hash, n_fragments), the members in struct order
+        off, length, _, nfrag = records
+    n = off.numel()
+    for t, size in ((off, 8), (length, 8), (nfrag, 4)):
+        assert t.device == log.device, (t.device, log.device)
+        _out(t, n, size)
+        assert t.numel() == n, (t.numel(), n)
+    dev = log.device
+    rep_off = torch.empty(n, dtype=torch.int64, device=dev)
+    rep_size = torch.empty(n, dtype=torch.int32, device=dev)
+    status = torch.empty(n, dtype=torch.uint8, device=dev)
+    total = ctypes.c_uint64()
+    args = (log.data_ptr(), log.numel(), off.data_ptr(), length.data_ptr(), nfrag.data_ptr(), n)
+    outs = (rep_off.data_ptr(), rep_size.data_ptr(), status.data_ptr(), ctypes.byref(total),
+            _stream(stream))
+    if arena is None:
+        check(lib().forst_wal_records_compact(*args, None, 0, *outs))
+        arena = torch.empty(max(16, total.value), dtype=torch.uint8, device=dev)
+    assert arena.device == dev and arena.dtype == torch.uint8 and arena.is_contiguous()
+    rc = lib().forst_wal_records_compact(*args, arena.data_ptr(), arena.numel(), *outs)
+    check(rc, arena_bytes=total.value)
+    return arena[:total.value], rep_off, rep_size, status
+
+
 def hash64_batch(base, offsets, lengths, seeds=None, seed=0, out=None, stream=None):
     """Hash64 / NPHash64 per buffer (util/hash.cc:81, XXPH3 0.7.2 preview)."""
     n = _desc(offsets, lengths)

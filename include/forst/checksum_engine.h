@@ -307,6 +307,19 @@ struct WalRecord {
   uint32_t n_fragments = 0;
   std::vector<WalReport> reports_before;
 };
+// The records of a Recover, joined on the device (CompactRecords): record i's
+// bytes are arena[rep_offsets[i] .. + rep_sizes[i]), every rep on a 16-byte
+// boundary with zero padding behind it; status[i] != 0 (and size 0) where the
+// record's layout could not be followed (forst_wal_records_compact).  All
+// pointers are DEVICE pointers owned by the WalRecovery.
+struct WalDeviceRecords {
+  const uint8_t* arena = nullptr;
+  uint64_t arena_bytes = 0;
+  const uint64_t* rep_offsets = nullptr;
+  const uint32_t* rep_sizes = nullptr;
+  const uint8_t* status = nullptr;
+  uint64_t n = 0;
+};
 class WalRecovery {
  public:
   explicit WalRecovery(void* hip_stream = nullptr) : stream_(hip_stream) {}
@@ -323,12 +336,24 @@ class WalRecovery {
   // false after the last record; status() is then OK unless the record
   // layout could not be followed on the host (NotSupported: fall back)
   bool Next(WalRecord* r);
+  // Next() without the bytes (r->data == nullptr, nothing is joined): the
+  // record's size, offset, checksum, fragment count and reports_before, for a
+  // caller that takes the bytes from CompactRecords.  Shares Next()'s position.
+  bool NextMeta(WalRecord* r);
+  // The bytes Next() hands out, for every record of the last Recover, joined
+  // on the device instead: the records as contiguous reps in device memory
+  // (what KvProtection::WriteBatchProtectionDevice and forst_xxh3_64_batch
+  // take), the log never leaving it.  d_log: the device log Recover was given.
+  // *out stays valid until the next Recover or CompactRecords.  Synchronises
+  // the stream.
+  Status CompactRecords(const uint8_t* d_log, WalDeviceRecords* out);
   const std::vector<WalReport>& trailing_reports() const { return trailing_; }
   const Status& status() const { return status_; }
   const forst_wal_recover_result& result() const { return res_; }
 
  private:
   Status Grow(uint64_t rec_cap, uint64_t rep_cap);
+  bool Step(WalRecord* r, bool join);
   void* stream_;
   const uint8_t* host_ = nullptr;
   uint64_t len_ = 0;
@@ -341,6 +366,10 @@ class WalRecovery {
   Status status_;
   void* dev_ = nullptr;  // device arrays (records, then reports)
   uint64_t rec_cap_ = 0, rep_cap_ = 0;
+  void* reps_ = nullptr;  // CompactRecords: offsets, sizes, status
+  uint64_t reps_cap_ = 0;
+  void* arena_ = nullptr;  // ... and the record bytes
+  uint64_t arena_cap_ = 0;
 };
 
 // Write side: log::Writer::AddRecord (db/log_writer.cc:65-160) +
@@ -393,6 +422,9 @@ class WalWriteGroup {
 //   WriteBatchProtection   WriteBatchInternal::UpdateProtectionInfo(wb, 8)
 //     (db/write_batch.cc:3164-3181): each rep's ProtectionInfoKVOC64 values in
 //     record order and its Iterate status (forst_write_batch_protect_batch)
+//   WriteBatchProtectionDevice  the same over reps that already lie in DEVICE
+//     memory (d_base[d_rep_offsets[b] .. + d_rep_sizes[b]), device arrays:
+//     e.g. WalRecovery::CompactRecords' arena): nothing is staged
 struct KvBytes {
   const char* data;
   size_t size;
@@ -413,6 +445,10 @@ class KvProtection {
   Status WriteBatchProtection(const std::vector<KvBytes>& reps,
                               std::vector<std::vector<uint64_t>>* prot,
                               std::vector<Status>* rep_status);
+  Status WriteBatchProtectionDevice(const uint8_t* d_base, uint64_t base_len,
+                                    const uint64_t* d_rep_offsets, const uint32_t* d_rep_sizes,
+                                    uint64_t n, std::vector<std::vector<uint64_t>>* prot,
+                                    std::vector<Status>* rep_status);
   // the Corruption text of a WriteBatch status code (write_batch.cc:361-716)
   static Status WriteBatchStatus(uint8_t code);
 

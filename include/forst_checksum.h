@@ -70,9 +70,9 @@
  *    forst_wal_verify_batch, forst_wal_record_xxh3_batch and
  *    forst_wal_recover_batch, which read counts back (1, 2 and 4 stream
  *    synchronisations per call: record total; logical records + gathered
- *    bytes; items, tokens, emitted counts, gathered bytes), and the
- *    explicitly synchronous host-memory / SST-file / table-writer entry
- *    points below.
+ *    bytes; items, tokens, emitted counts, gathered bytes),
+ *    forst_wal_records_compact (1: the arena total), and the explicitly
+ *    synchronous host-memory / SST-file / table-writer entry points below.
  *  - `base` must be 4-byte aligned; blocks live at base + offsets[i] and may
  *    start at any byte (SST blocks are packed back-to-back with 5-byte
  *    trailers, so starts are unaligned).  base_len bounds every access: a
@@ -356,6 +356,42 @@ int forst_wal_recover_batch(const uint8_t* log, uint64_t log_len, uint32_t log_n
                             uint64_t record_capacity, forst_wal_reports reports,
                             uint64_t report_capacity, forst_wal_recover_result* result,
                             void* stream);
+
+/* The bytes log::Reader::ReadRecord returns for each given record (its
+ * `record` Slice / scratch), contiguous in `arena`: the reps
+ * forst_write_batch_protect_batch and forst_xxh3_64_batch take, without the
+ * log leaving device memory.  rec_offset / rec_length / rec_n_fragments are
+ * device arrays as forst_wal_recover_batch writes them (offset, length,
+ * n_fragments): any subset of a log's records in any order, each record on its
+ * own.  From rec_offset the physical records are followed as the reader
+ * follows them: a block tail shorter than a header and a recyclable writer's
+ * 7..10-byte zero tail are skipped, control records (types 9-11) are stepped
+ * over uncounted, rec_n_fragments data fragments are taken, with the header
+ * size of their type byte.
+ * Outputs (device, each nullable):
+ *   rep_sizes[i]    the record's length; 0 when status[i] != 0
+ *   rep_offsets[i]  the exclusive prefix sum of round_up(rep_sizes, 16): every
+ *                   rep starts on a 16-byte boundary of the arena, and the up
+ *                   to 15 bytes behind it are written as zero
+ *   status[i]       0 OK; 1 the layout cannot be followed (the walk leaves
+ *                   log_len, meets a type that is neither data nor control
+ *                   before it has its fragments, or the payloads do not add up
+ *                   to rec_length); 2 the record is longer than 2^32 - 1 bytes.
+ *                   For 1 and 2 nothing outside the log is read and nothing is
+ *                   written to the arena.
+ * Arena bytes at and past *arena_bytes are not touched.
+ * Synchronous: *arena_bytes (host, required) = the bytes used.  With arena ==
+ * NULL and arena_capacity == 0 the call only fills rep_offsets, rep_sizes,
+ * status and *arena_bytes; FORST_EINVAL, with *arena_bytes set and the arena
+ * untouched, when a given arena is smaller (log_len + 15 * n_records always
+ * suffices).  arena must be 16-byte aligned, log 4-byte aligned, and the arena
+ * must not overlap the log (FORST_EINVAL).  n_records == 0 sets *arena_bytes =
+ * 0 and touches nothing else. */
+int forst_wal_records_compact(const uint8_t* log, uint64_t log_len, const uint64_t* rec_offset,
+                              const uint64_t* rec_length, const uint32_t* rec_n_fragments,
+                              uint64_t n_records, uint8_t* arena, uint64_t arena_capacity,
+                              uint64_t* rep_offsets, uint32_t* rep_sizes, uint8_t* status,
+                              uint64_t* arena_bytes, void* stream);
 
 /* Host utility (no GPU call): the physical-record layout log::Writer::AddRecord
  * produces for logical records of the given lengths (db/log_writer.cc:65-160,
