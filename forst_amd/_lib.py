@@ -122,6 +122,8 @@ def lib():
         "forst_blob_walk_file": (i, [vp, u64, vp, vp, u64, vp, vp, vp]),
         "forst_blob_verify_files": (i, [vp, vp, vp, vp, u64, vp, u64, vp, vp]),
         "forst_wal_records_compact": (i, [vp, u64, vp, vp, vp, u64, vp, u64, vp, vp, vp, vp, vp]),
+        "forst_wal_frame_batch": (i, [vp, u64, vp, vp, vp, u64, i, u32, u32, vp, u64, vp, vp, vp,
+                                      vp, u64, vp, vp, vp]),
         "forst_wal_recover_batch": None,  # struct arguments: argtypes set by engine
     }
     for name, sig in sigs.items():

@@ -5,9 +5,9 @@
 // (hipMallocFromPoolAsync / hipFreeAsync).  The block, raw-hash, combine, KV
 // and WAL-writer entry points never copy to the host or synchronise, so they
 // can be captured into hipGraphs (cdna_hip_programming.md Guideline 9);
-// forst_wal_verify_batch, forst_wal_record_xxh3_batch, forst_wal_recover_batch
-// and forst_wal_records_compact read a count back (at least one stream
-// synchronisation each) and cannot be.
+// forst_wal_verify_batch, forst_wal_record_xxh3_batch, forst_wal_recover_batch,
+// forst_wal_records_compact and forst_wal_frame_batch read a count back (at
+// least one stream synchronisation each) and cannot be.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -581,6 +581,63 @@ FORST_API int forst_wal_records_compact(const uint8_t* log, uint64_t log_len,
     return set_error(FORST_EINVAL, "arena_capacity " + std::to_string(arena_capacity) + " < " +
                                        std::to_string(total) + " arena bytes");
   return hip_status(e, "wal_records_compact");
+}
+
+FORST_API int forst_wal_frame_batch(const uint8_t* base, uint64_t base_len,
+                                    const uint64_t* rep_offsets, const uint32_t* rep_sizes,
+                                    const uint32_t* host_sizes, uint64_t n_records,
+                                    int recyclable, uint32_t log_number, uint32_t block_offset,
+                                    uint8_t* image, uint64_t image_capacity,
+                                    uint64_t* rec_offsets, uint64_t* phys_offsets,
+                                    uint32_t* phys_lengths, uint8_t* phys_types,
+                                    uint64_t phys_capacity, uint8_t* status,
+                                    forst_wal_frame_result* result, void* stream) {
+  if (!result) return set_error(FORST_EINVAL, "result must be non-null");
+  *result = forst_wal_frame_result{};
+  if (block_offset > 32768)  // (forst_wal_layout_at's rule)
+    return set_error(FORST_EINVAL, "block_offset " + std::to_string(block_offset) + " > 32768");
+  result->end_block_offset = block_offset;
+  if (n_records == 0) return FORST_OK;
+  if (!base || !rep_offsets || !rep_sizes)
+    return set_error(FORST_EINVAL, "base/rep_offsets/rep_sizes must be non-null");
+  if (!image && image_capacity) return set_error(FORST_EINVAL, "image must be non-null");
+  if (reinterpret_cast<uintptr_t>(image) & 15)
+    return set_error(FORST_EINVAL, "image must be 16-byte aligned");
+  if (image && base_len && image_capacity) {
+    const uintptr_t i0 = reinterpret_cast<uintptr_t>(image), b0 = reinterpret_cast<uintptr_t>(base);
+    if (i0 < b0 + base_len && b0 < i0 + image_capacity)
+      return set_error(FORST_EINVAL, "image overlaps base");
+  }
+  int rc = check_device();
+  if (rc) return rc;
+  FrArgs a{};
+  a.base = base;
+  a.base_len = base_len;
+  a.rep_offsets = rep_offsets;
+  a.rep_sizes = rep_sizes;
+  a.host_sizes = host_sizes;
+  a.n = n_records;
+  a.recyclable = recyclable ? 1 : 0;
+  a.log_number = log_number;
+  a.block_offset = block_offset;
+  a.image = image;
+  a.capacity = image_capacity;
+  a.rec_offsets = rec_offsets;
+  a.phys_offsets = phys_offsets;
+  a.phys_lengths = phys_lengths;
+  a.phys_types = phys_types;
+  a.phys_capacity = phys_capacity;
+  a.status = status;
+  const hipError_t e = launch_wal_frame(a, static_cast<hipStream_t>(stream), result,
+                                        &g_last_kernel);
+  if (e == hipErrorInvalidValue && (phys_offsets || phys_lengths || phys_types) &&
+      phys_capacity < result->n_physical)
+    return set_error(FORST_EINVAL, "phys_capacity " + std::to_string(phys_capacity) + " < " +
+                                       std::to_string(result->n_physical) + " physical records");
+  if (e == hipErrorInvalidValue && image && result->image_bytes > image_capacity)
+    return set_error(FORST_EINVAL, "image_capacity " + std::to_string(image_capacity) + " < " +
+                                       std::to_string(result->image_bytes) + " image bytes");
+  return hip_status(e, "wal_frame");
 }
 
 // ---- blob file records (blob.h, blob_host.h) ---------------------------------

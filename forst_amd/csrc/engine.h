@@ -296,6 +296,33 @@ struct WcArgs {
 hipError_t launch_wal_records_compact(const WcArgs& a, hipStream_t st, uint64_t* total,
                                       const char** kernel_name);
 
+// forst_wal_frame_batch (wal_frame.h, compiled into wal.hip)
+struct FrArgs {
+  const uint8_t* base;
+  uint64_t base_len;
+  const uint64_t* rep_offsets;  // device, n
+  const uint32_t* rep_sizes;    // device, n
+  const uint32_t* host_sizes;   // host copy of rep_sizes, nullable (read back then)
+  uint64_t n;
+  int recyclable;
+  uint32_t log_number;
+  uint32_t block_offset;        // <= 32768
+  uint8_t* image;               // nullable: the result and the descriptors only
+  uint64_t capacity;
+  uint64_t* rec_offsets;        // out, nullable, n
+  uint64_t* phys_offsets;       // out, nullable, phys_capacity
+  uint32_t* phys_lengths;
+  uint8_t* phys_types;
+  uint64_t phys_capacity;
+  uint8_t* status;              // out, nullable, n
+};
+// synchronous; *res (zeroed by the caller) is filled from the host placement.
+// hipErrorInvalidValue: descriptor arrays given and phys_capacity <
+// res->n_physical (nothing written), or an image given and capacity <
+// res->image_bytes (the image untouched)
+hipError_t launch_wal_frame(const FrArgs& a, hipStream_t st, forst_wal_frame_result* res,
+                            const char** kernel_name);
+
 struct DeviceInfo {
   int device;
   int num_cus;

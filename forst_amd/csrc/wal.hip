@@ -543,3 +543,5 @@ hipError_t launch_wal_record_xxh3(const WalArgs& a, uint64_t* out, uint64_t* out
 #include "blob.h"
 // recovered records as contiguous reps (launch_wal_records_compact)
 #include "wal_compact.h"
+// reps framed into the log image, the inverse (launch_wal_frame)
+#include "wal_frame.h"

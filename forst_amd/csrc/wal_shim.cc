@@ -353,6 +353,51 @@ Status WalWriteGroup::Frame(const std::vector<ByteRange>& records, uint32_t bloc
   return Status::OK();
 }
 
+// The placement-only call (no image, no descriptor array) sizes the device
+// buffer; the second call frames into it.
+Status WalWriteGroup::FrameDevice(const uint8_t* d_base, uint64_t base_len,
+                                  const uint64_t* d_rep_offsets, const uint32_t* d_rep_sizes,
+                                  const uint32_t* host_sizes, uint64_t n, uint32_t block_offset) {
+  image_.clear();
+  offs_.clear();
+  d_image_ = nullptr;
+  d_size_ = d_np_ = d_bad_ = 0;
+  std::vector<uint32_t> sizes;
+  if (n && !host_sizes && d_rep_sizes) {  // one read-back here instead of one per call below
+    sizes.resize(n);
+    Status s = FromHip(hipMemcpy(sizes.data(), d_rep_sizes, n * 4, hipMemcpyDeviceToHost),
+                       "hipMemcpy");
+    if (!s.ok()) return s;
+    host_sizes = sizes.data();
+  }
+  forst_wal_frame_result res;
+  Status s = FromRc(forst_wal_frame_batch(d_base, base_len, d_rep_offsets, d_rep_sizes, host_sizes,
+                                          n, recyclable_, log_number_, block_offset, nullptr, 0,
+                                          nullptr, nullptr, nullptr, nullptr, 0, nullptr, &res,
+                                          stream_));
+  if (!s.ok()) return s;
+  end_bo_ = res.end_block_offset;
+  if (res.image_bytes == 0) return Status::OK();
+  if (res.image_bytes > dev_cap_) {
+    (void)hipFree(dev_);
+    dev_ = nullptr;
+    dev_cap_ = 0;
+    s = FromHip(hipMalloc(&dev_, res.image_bytes), "hipMalloc");
+    if (!s.ok()) return s;
+    dev_cap_ = res.image_bytes;
+  }
+  s = FromRc(forst_wal_frame_batch(d_base, base_len, d_rep_offsets, d_rep_sizes, host_sizes, n,
+                                   recyclable_, log_number_, block_offset,
+                                   static_cast<uint8_t*>(dev_), dev_cap_, nullptr, nullptr, nullptr,
+                                   nullptr, 0, nullptr, &res, stream_));
+  if (!s.ok()) return s;
+  d_image_ = static_cast<const uint8_t*>(dev_);
+  d_size_ = res.image_bytes;
+  d_np_ = res.n_physical;
+  d_bad_ = res.bad_records;
+  return Status::OK();
+}
+
 }  // namespace forst_gpu
 
 // ---- per-KV protection at its call sites (a15) ------------------------------

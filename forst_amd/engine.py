@@ -420,6 +420,59 @@ def wal_records_compact(log, records, arena=None, stream=None):
     return arena[:total.value], rep_off, rep_size, status
 
 
+class WalFrameResult(ctypes.Structure):
+    """forst_wal_frame_result"""
+    _fields_ = [("image_bytes", ctypes.c_uint64), ("n_physical", ctypes.c_uint64),
+                ("n_pads", ctypes.c_uint64), ("bad_records", ctypes.c_uint64),
+                ("end_block_offset", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+def wal_frame_batch(base, rep_offsets, rep_sizes, recyclable, log_number, block_offset=0,
+                    image=None, host_sizes=None, stream=None):
+    """What log::Writer::AddRecord appends for the records
+    base[rep_offsets[i]:rep_offsets[i] + rep_sizes[i]] (device tensors, the
+    shape wal_records_compact returns and write_batch_protect_batch takes),
+    framed on the device from block_offset (forst_wal_frame_batch): payloads,
+    headers with their CRCs, zero block tails.  Returns (image, desc, result):
+    the image cut to the appended bytes; desc with rec_offsets int64 [n],
+    phys_offsets int64 / phys_lengths int32 / phys_types uint8 [n_physical]
+    and status uint8 [n] (1: the rep reaches past base, framed as zeros);
+    result a WalFrameResult.  image: the caller's own uint8 tensor (16-byte
+    aligned, apart from base); one below the total raises a ForstError whose
+    image_bytes is the size to call again with.  host_sizes: a CPU copy of
+    rep_sizes (int32 tensor), read back from the device when left out.
+    Synchronous."""
+    _dev_u8(base)
+    n = _desc(rep_offsets, rep_sizes)
+    dev = base.device
+    assert rep_offsets.device == dev and rep_sizes.device == dev, (rep_offsets.device, dev)
+    if host_sizes is None:
+        host_sizes = rep_sizes.cpu()
+    assert not host_sizes.is_cuda and host_sizes.dtype in (torch.int32, torch.uint32)
+    assert host_sizes.is_contiguous() and host_sizes.numel() == n, (host_sizes.numel(), n)
+    res = WalFrameResult()
+    args = (base.data_ptr(), base.numel(), rep_offsets.data_ptr(), rep_sizes.data_ptr(),
+            host_sizes.data_ptr(), n, int(bool(recyclable)), log_number, block_offset)
+    # the placement alone: sizes the image and the descriptor arrays
+    check(lib().forst_wal_frame_batch(*args, None, 0, None, None, None, None, 0, None,
+                                      ctypes.byref(res), _stream(stream)))
+    nph = res.n_physical
+    if image is None:
+        image = torch.empty(max(16, res.image_bytes), dtype=torch.uint8, device=dev)
+    assert image.device == dev and image.dtype == torch.uint8 and image.is_contiguous()
+    desc = {"rec_offsets": torch.empty(n, dtype=torch.int64, device=dev),
+            "phys_offsets": torch.empty(nph, dtype=torch.int64, device=dev),
+            "phys_lengths": torch.empty(nph, dtype=torch.int32, device=dev),
+            "phys_types": torch.empty(nph, dtype=torch.uint8, device=dev),
+            "status": torch.empty(n, dtype=torch.uint8, device=dev)}
+    rc = lib().forst_wal_frame_batch(
+        *args, image.data_ptr(), image.numel(), _p(desc["rec_offsets"]), _p(desc["phys_offsets"]),
+        _p(desc["phys_lengths"]), _p(desc["phys_types"]), nph, _p(desc["status"]),
+        ctypes.byref(res), _stream(stream))
+    check(rc, image_bytes=res.image_bytes)
+    return image[:res.image_bytes], desc, res
+
+
 def hash64_batch(base, offsets, lengths, seeds=None, seed=0, out=None, stream=None):
     """Hash64 / NPHash64 per buffer (util/hash.cc:81, XXPH3 0.7.2 preview)."""
     n = _desc(offsets, lengths)

@@ -380,6 +380,15 @@ class WalRecovery {
 // CRC in one GPU launch (forst_wal_record_crc_batch) and puts them in the
 // headers: data()/size() is what AddRecord would have appended, record by
 // record, and end_block_offset() the writer's block_offset_ afterwards.
+// FrameDevice() frames reps that already lie in DEVICE memory
+// (d_base[d_rep_offsets[i] .. + d_rep_sizes[i]), device arrays -- the staged
+// copy KvProtection::WriteBatchProtectionDevice reads, or
+// WalRecovery::CompactRecords' arena) without the bytes touching the host
+// (forst_wal_frame_batch): device_data()/size() is the same image in device
+// memory, owned by the object until its next call.  host_sizes: a host copy
+// of d_rep_sizes, or nullptr (read back then).  bad_records(): reps that
+// reached past base_len and were framed as zeros.  An object serves Frame()
+// or FrameDevice(), not both in turn.
 struct ByteRange {
   const char* data;
   size_t size;
@@ -392,10 +401,15 @@ class WalWriteGroup {
   WalWriteGroup(const WalWriteGroup&) = delete;
   WalWriteGroup& operator=(const WalWriteGroup&) = delete;
   Status Frame(const std::vector<ByteRange>& records, uint32_t block_offset);
+  Status FrameDevice(const uint8_t* d_base, uint64_t base_len, const uint64_t* d_rep_offsets,
+                     const uint32_t* d_rep_sizes, const uint32_t* host_sizes, uint64_t n,
+                     uint32_t block_offset);
   const char* data() const { return image_.data(); }
-  size_t size() const { return image_.size(); }
+  const uint8_t* device_data() const { return d_image_; }
+  size_t size() const { return d_image_ ? d_size_ : image_.size(); }
   uint32_t end_block_offset() const { return end_bo_; }
-  uint64_t physical_records() const { return offs_.size(); }
+  uint64_t physical_records() const { return d_image_ ? d_np_ : offs_.size(); }
+  uint64_t bad_records() const { return d_bad_; }
 
  private:
   bool recyclable_;
@@ -406,6 +420,8 @@ class WalWriteGroup {
   uint32_t end_bo_ = 0;
   void* dev_ = nullptr;
   uint64_t dev_cap_ = 0;
+  const uint8_t* d_image_ = nullptr;  // FrameDevice: the image in dev_
+  uint64_t d_size_ = 0, d_np_ = 0, d_bad_ = 0;
 };
 
 

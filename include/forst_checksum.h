@@ -414,6 +414,59 @@ int forst_wal_layout_at(const uint32_t* lengths, uint64_t n_records, int recycla
                         uint32_t* pad_lengths, uint64_t pad_capacity, uint64_t* n_phys,
                         uint64_t* n_pads, uint64_t* total_bytes, uint32_t* end_block_offset);
 
+/* WAL write side on device reps: what log::Writer::AddRecord
+ * (db/log_writer.cc:65-160) and EmitPhysicalRecord (:228-263) append for the
+ * logical records base[rep_offsets[i] .. + rep_sizes[i]) -- the (base,
+ * rep_offsets, rep_sizes) forst_wal_records_compact writes and
+ * forst_write_batch_protect_batch reads, reps at any byte alignment --
+ * produced in `image` (device): the payloads, the [masked CRC][len LE16][type]
+ * [log number when recyclable] headers and the zero pads of 1..hs-1 bytes at
+ * block tails (hs = 7, or 11 when recyclable), byte for byte.  The image holds
+ * the appended bytes only: its offset 0 is the writer's append position,
+ * `block_offset` (log::Writer::block_offset_, <= 32768 as for
+ * forst_wal_layout_at, FORST_EINVAL otherwise) into the current 32 KiB block.
+ * host_sizes is a host copy of rep_sizes (the placement is a serial walk over
+ * the sizes, done on the host); NULL: the call reads rep_sizes back itself
+ * (one more stream synchronisation).
+ * Outputs (device, each nullable):
+ *   rec_offsets[i]   image offset of record i's first header
+ *   phys_offsets / phys_lengths / phys_types (phys_capacity entries each):
+ *                    every physical record in log order, identical to
+ *                    forst_wal_layout_at's rec_offsets / rec_lengths / rec_types
+ *   status[i]        0 OK; 1 the rep reaches past base_len: the record is laid
+ *                    out with its length all the same (the layout depends on
+ *                    the sizes alone), its payload is written as zeros and its
+ *                    CRCs cover those zeros; nothing outside base is read
+ * *result (host, required) is filled from the placement before anything runs
+ * on the device, so it is valid on FORST_EINVAL too (bad_records excepted).
+ * Synchronous.  With image == NULL and image_capacity == 0 the call fills only
+ * *result and the descriptor outputs.  FORST_EINVAL, the image untouched (the
+ * descriptor outputs filled), when a given image is smaller than
+ * result->image_bytes; FORST_EINVAL, nothing written, when a phys_* array is
+ * given and phys_capacity < result->n_physical.  On success every byte of
+ * image[0, image_bytes) is written and no byte at or past image_bytes is
+ * touched (the CRC pass, which reads whole dwords like every record-CRC call,
+ * reads -- never writes -- the up to 3 bytes that complete the last dword of
+ * an image whose size is no multiple of 4: inside any device allocation).
+ * image must be 16-byte aligned and must not overlap base
+ * (FORST_EINVAL).  n_records == 0 gives image_bytes = 0 (end_block_offset =
+ * block_offset) and touches nothing else. */
+typedef struct forst_wal_frame_result {
+  uint64_t image_bytes;       /* bytes appended */
+  uint64_t n_physical;        /* physical records (headers) */
+  uint64_t n_pads;            /* zero-filled block tails */
+  uint64_t bad_records;       /* records with status 1 */
+  uint32_t end_block_offset;  /* block_offset_ behind the last record */
+  uint32_t reserved;
+} forst_wal_frame_result;
+int forst_wal_frame_batch(const uint8_t* base, uint64_t base_len, const uint64_t* rep_offsets,
+                          const uint32_t* rep_sizes, const uint32_t* host_sizes,
+                          uint64_t n_records, int recyclable, uint32_t log_number,
+                          uint32_t block_offset, uint8_t* image, uint64_t image_capacity,
+                          uint64_t* rec_offsets, uint64_t* phys_offsets, uint32_t* phys_lengths,
+                          uint8_t* phys_types, uint64_t phys_capacity, uint8_t* status,
+                          forst_wal_frame_result* result, void* stream);
+
 /* NPHash64 / Hash64 (util/hash.h:45-62, util/hash.cc:81 ->
  * XXPH3_64bits_withSeed, util/xxph3.h:1733; xxHash 0.7.2 preview):
  * out[i] = Hash64(base + offsets[i], lengths[i], seeds ? seeds[i] : seed).
